@@ -16,6 +16,12 @@ timed record is checked against the same clip's one-clip-per-launch record (ever
 `single_clip_ms_per_step` is the one-clip-per-launch pipeline of rounds 1-4 beside it.  Inputs are resident in HBM before the
 timed region.  Clips shard over ranks (weak scaling: K clips per rank, no data-path collective);
 the single result all_gather sits inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  `--full` adds
+everything else this file measures or checks after the timed region: the streamed, f32-only and single-clip passes, the long
+run, the slot check, the per-family rooflines, the parity against the reference golden and the CPU oracle, the CPU baseline
+and the --detail file.  `--dump-outputs DIR` writes the last timed step's outputs (selected query, its class logits, its mask
+logits) as DIR/<name>.npy; the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -81,6 +87,11 @@ def parse():
                     help="pair pipeline: skip the extra timed pass with one clip per head launch (single_clip_ms_per_step)")
     ap.add_argument("--no-f32-pass", action="store_true",
                     help="skip the extra timed pass with every GEMM on the f32 MFMA path (SOC_MATMUL=f32 arithmetic)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the extra timed passes, rooflines, parity checks, CPU baseline and the --detail "
+                         "file (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -259,6 +270,18 @@ def emit(line, full, detail_path):
         text = json.dumps(line)
     sys.stderr.flush()
     print(text, flush=True)
+
+
+def dump_outputs(dirname, record, T, Q, hm, wm):
+    """--dump-outputs: one timed clip's record unpacked into what a caller of the timed path receives -- the selected query,
+    its class logits per frame [T, Q] and its mask logits at 1/4 resolution [T, hm, wm] -- one .npy file each."""
+    import numpy as np
+    from neurips2023_soc_amd.clip_parallel import unpack_record
+    q, cls, masks = unpack_record(record, T, Q, hm, wm)
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in (("selected_query", np.array([q], dtype=np.float64)), ("pred_cls", cls.numpy().astype(np.float32)),
+                      ("selected_masks", masks.numpy().astype(np.float32))):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def stub_main(a, CP):
@@ -445,13 +468,39 @@ def main():
     torch.cuda.synchronize()
     results.zero_()                 # what is checked below can only have been written by the timed region
 
-    if graph is None:
+    if graph is None and a.full:
         hot_ops.profile_begin()
     # barrier + sync | exactly K clips (pipeline drained) + the one result all_gather | barrier + sync; max over ranks
     timed = CP.timed_sharded_run(lambda out: run_steps(a.steps, out), results, dev)
     gathered, dt = timed["gathered"], timed["seconds"]
     timed_records = results[:min(a.steps, n_pool)].cpu()      # clip i of the pool <-> record i
     all_timed_records = results.cpu()                         # record i <-> pool clip i % n_pool: every one is checked below
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, all_timed_records[a.steps - 1], T, Q, hm, wm)
+    assert gathered.shape[0] == world == a.gpus and timed["ranks_seen"] == list(range(world)), timed["ranks_seen"]
+
+    workload = (f"SOC eval forward + query selection per clip (one clip + one expression = the reference's B=1 forward), "
+                f"{a.backbone}, T={T}, {H}x{Wd}, L={L} tokens, random deterministic weights (seed {WEIGHT_SEED})"
+                + (f"; {per} independent clips share each head launch" if per > 1 else ""))
+    launch = ("eager" if graph is None else (
+        ("hipGraph replays, software-pipelined on two streams: Video-Swin + fusion + encoder of clip i | text "
+         "encoder of clip i, tail of clip i-1" if Pipeline.__name__ == "TwoStreamClipGraph" else
+         f"hipGraph replay, software-pipelined, {Pipeline.CLIPS} independent clips per launch group: head (Video-Swin, fusion, "
+         "encoder) of group i beside the tail of group i-1, VOC -- the one module of the reference that couples "
+         "a batch -- run per clip" if Pipeline.CLIPS > 1 else
+         "hipGraph replay, software-pipelined: tail of clip i beside the head of clip i+1")
+        if pipelined else "hipGraph replay (one graph per clip geometry)"))
+    matmul = (("f32 in / out / accumulate; large products as 6 bf16 MFMA products of a 3-way operand split (f32-grade: "
+               "error vs f64 <= the f32 library GEMM's, test_linear_split_is_f32_grade); f32_mfma_only_* = no split")
+              if hot_ops.split_enabled() else "f32 MFMA (SOC_MATMUL=f32)")
+    if not a.full:
+        # the headline only: everything below (extra passes, rooflines, parity, CPU baseline) is --full
+        if rank == 0:
+            emit(compact_line({**headline(a, world, timed, workload, launch), "matmul": matmul, "clips_per_head_launch": per}),
+                 None, None)
+        if use_dist:
+            dist.destroy_process_group()
+        return 0
 
     # Second timed pass, H2D-inclusive (SURVEY 8d config 5 "stream with per-clip seeds seed0 + i", 8e "pinned,
     # double-buffered H2D"): the same loop, but every clip is copied from a pinned host buffer inside the timed region.
@@ -628,25 +677,10 @@ def main():
         families[fam] = {"ms": ms, "launches": len(calls), "shapes": shapes}      # ms, launches: of ONE replay = `per` clips
         del calls[:]
 
-    assert gathered.shape[0] == world == a.gpus and timed["ranks_seen"] == list(range(world)), timed["ranks_seen"]
-
     if rank == 0:
         line = {
-            **headline(a, world, timed,
-                       f"SOC eval forward + query selection per clip (one clip + one expression = the reference's B=1 forward), "
-                       f"{a.backbone}, T={T}, {H}x{Wd}, L={L} tokens, random deterministic weights (seed {WEIGHT_SEED})"
-                       + (f"; {per} independent clips share each head launch" if per > 1 else ""),
-                       "eager" if graph is None else (
-                           ("hipGraph replays, software-pipelined on two streams: Video-Swin + fusion + encoder of clip i | text "
-                            "encoder of clip i, tail of clip i-1" if Pipeline.__name__ == "TwoStreamClipGraph" else
-                            f"hipGraph replay, software-pipelined, {Pipeline.CLIPS} independent clips per launch group: head (Video-Swin, fusion, "
-                            "encoder) of group i beside the tail of group i-1, VOC -- the one module of the reference that couples "
-                            "a batch -- run per clip" if Pipeline.CLIPS > 1 else
-                            "hipGraph replay, software-pipelined: tail of clip i beside the head of clip i+1")
-                           if pipelined else "hipGraph replay (one graph per clip geometry)")),
-            "matmul": ("f32 in / out / accumulate; large products as 6 bf16 MFMA products of a 3-way operand split (f32-grade: "
-                       "error vs f64 <= the f32 library GEMM's, test_linear_split_is_f32_grade); f32_mfma_only_* = no split")
-                      if hot_ops.split_enabled() else "f32 MFMA (SOC_MATMUL=f32)",
+            **headline(a, world, timed, workload, launch),
+            "matmul": matmul,
             **({"f32_mfma_only_ms_per_step": 1e3 * f32_pass["seconds"] / a.steps,
                 "f32_mfma_only_value": world * a.steps / f32_pass["seconds"],
                 "f32_mfma_only_record0_max_abs_diff": float((f32_pass["record0"] - timed_records[0]).abs().max())}

@@ -152,3 +152,29 @@ def test_default_pipeline_is_a_fixed_group():
     from neurips2023_soc_amd import graph_runner
     for name, clips in (("group10", 10), ("octs", 8), ("quads", 4), ("pairs", 2), ("group3", 3), ("one-graph", 1)):
         assert graph_runner.pipeline_class(name).CLIPS == clips
+
+
+def test_dump_outputs_writes_the_unpacked_record(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: one timed record unpacked into selected query, class logits and mask logits, float32 / float64
+    .npy files that hold exactly what the record held; `--full` and `--dump-outputs` are parsed, off by default."""
+    import numpy as np
+    import sys
+    import torch
+    from neurips2023_soc_amd import clip_parallel as CP
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "x")])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "x")
+    T, Q, hm, wm = 2, 3, 4, 5
+    g = torch.Generator().manual_seed(7)
+    cls, masks = torch.randn(T, Q, generator=g), torch.randn(T, hm, wm, generator=g)
+    rec = torch.zeros(CP.record_size(T, Q, hm, wm))
+    CP.pack_record(rec, torch.tensor(2), cls, masks)
+    bench.dump_outputs(a.dump_outputs, rec, T, Q, hm, wm)
+    got = {n: np.load(tmp_path / "x" / f"{n}.npy") for n in ("selected_query", "pred_cls", "selected_masks")}
+    assert got["selected_query"].dtype == np.float64 and got["selected_query"].tolist() == [2.0]
+    assert got["pred_cls"].dtype == np.float32 and np.array_equal(got["pred_cls"], cls.numpy())
+    assert got["selected_masks"].dtype == np.float32 and np.array_equal(got["selected_masks"], masks.numpy())

@@ -178,7 +178,7 @@ def test_bench_under_torch_distributed_run_on_one_gpu():
     carries the rank-loop keys -- exercised every round while the 8-GPU run waits for a node."""
     port = CP.free_port()
     r = _run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-              "--master-port", str(port), "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline",
+              "--master-port", str(port), "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline",
               "--all-passes", "--no-stream", "--no-f32-pass", "--detail", ""], timeout=1500)
     line = _stub_line(r)
     assert "stub" not in line and line["n_gpus"] == 1 and line["ranks_seen"] == [0] and line["steps"] == 4

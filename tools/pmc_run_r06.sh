@@ -14,9 +14,9 @@ for part in $PARTS; do
 case $part in
 trace)
   # ---- (a) the headline command, plain and under the kernel tracer
-  python3 bench.py --steps 20 --warmup 5 --detail $P/bench_r06_n1_detail.json > $P/bench_r06_n1.json 2> $P/bench_r06_n1.err
-  python3 bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-stream --no-f32-pass --detail $P/bench_r06_n1_200steps_detail.json > $P/bench_r06_n1_200steps.json 2> /dev/null
-  rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- python3 bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-single-pass --detail $P/trace_bench_detail.json > $P/trace_bench.json 2> $P/trace_bench.err
+  python3 bench.py --full --steps 20 --warmup 5 --detail $P/bench_r06_n1_detail.json > $P/bench_r06_n1.json 2> $P/bench_r06_n1.err
+  python3 bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --no-stream --no-f32-pass --detail $P/bench_r06_n1_200steps_detail.json > $P/bench_r06_n1_200steps.json 2> /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- python3 bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-single-pass --detail $P/trace_bench_detail.json > $P/trace_bench.json 2> $P/trace_bench.err
   T=$(ls $P/trace/*/*kernel_trace.csv | head -1)
   cp $(ls $P/trace/*/*kernel_stats.csv | head -1) $P/r06_bench_kernel_stats.csv
   python3 tools/analyze_trace.py $T --top 30 > $P/r06_forward_breakdown.txt
@@ -25,8 +25,8 @@ trace)
   ;;
 traffic)
   # ---- (b) HBM traffic per kernel and clip at the launch-group shapes: FETCH_SIZE and WRITE_SIZE in separate passes
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/pmc_fetch -- python3 bench.py --eager --steps $GROUP --warmup $GROUP --no-cpu-baseline --no-stream --no-f32-pass --detail $P/pmc_fetch_detail.json > $P/pmc_fetch.log 2>&1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/pmc_write -- python3 bench.py --eager --steps $GROUP --warmup $GROUP --no-cpu-baseline --no-stream --no-f32-pass --detail $P/pmc_write_detail.json > $P/pmc_write.log 2>&1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/pmc_fetch -- python3 bench.py --full --eager --steps $GROUP --warmup $GROUP --no-cpu-baseline --no-stream --no-f32-pass --detail $P/pmc_fetch_detail.json > $P/pmc_fetch.log 2>&1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/pmc_write -- python3 bench.py --full --eager --steps $GROUP --warmup $GROUP --no-cpu-baseline --no-stream --no-f32-pass --detail $P/pmc_write_detail.json > $P/pmc_write.log 2>&1
   python3 tools/pmc_traffic.py $(ls $P/pmc_fetch/*/*counter_collection.csv | head -1) $(ls $P/pmc_write/*/*counter_collection.csv | head -1) $GROUP > $P/r06_hbm_traffic_pmc.json
   ;;
 counters)
@@ -70,7 +70,7 @@ swinb)
   #      (the bench lines with cpu_baseline + golden parity: profiles/bench_r06_swinb_*.json)
   for geo in 360p 720p; do
     if [ $geo = 720p ]; then G="--height 720 --width 1280 --steps 6"; PERG=2; else G="--steps 40"; PERG=$GROUP; fi
-    rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_swinb_$geo -- python3 bench.py --backbone video-swin-b $G --warmup 2 --no-cpu-baseline --no-stream --no-f32-pass --no-single-pass --detail $P/trace_swinb_${geo}_detail.json > $P/trace_swinb_$geo.json 2> $P/trace_swinb_$geo.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace_swinb_$geo -- python3 bench.py --full --backbone video-swin-b $G --warmup 2 --no-cpu-baseline --no-stream --no-f32-pass --no-single-pass --detail $P/trace_swinb_${geo}_detail.json > $P/trace_swinb_$geo.json 2> $P/trace_swinb_$geo.err
     cp $(ls $P/trace_swinb_$geo/*/*kernel_stats.csv | head -1) $P/r06_swinb_${geo}_kernel_stats.csv
     SOC_TRACE_CLIPS_PER_GROUP=$PERG python3 tools/analyze_trace.py $(ls $P/trace_swinb_$geo/*/*kernel_trace.csv | head -1) --top 25 > $P/r06_swinb_${geo}_forward_breakdown.txt
   done
