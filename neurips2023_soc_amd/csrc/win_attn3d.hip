@@ -866,488 +866,22 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_full_kernel(
 }
 
 // =============================================================================================
-// K1 on the bf16 matrix cores (round 3).  The f32-input MFMA above runs at the f32 vector rate (1/16 of the bf16 matrix
-// rate) and blocks the vector ALU while it runs; this form keeps f32 semantics -- every f32 operand is split EXACTLY
-// into three bf16 numbers (8 + 8 + 8 significant bits; csrc/linear_split.hip has the arithmetic), six of the nine
-// bf16 x bf16 products (each exact in f32) are accumulated in the f32 accumulators, the dropped three are <= 2^-23 |a b| --
-// at 6/16 of the matrix time and with the softmax's vector work running BESIDE the matrix cores instead of in front of
-// them.  Same algorithm and window enumeration as win_attn3d_full_kernel; what changes:
-//   * K and V of the head are split while they are staged: three planes each of [slot][32 dims] bf16 (64-B rows), 16-B
-//     chunk c of row r at chunk c ^ pi[(r >> 2) & 3], pi = (0, 3, 2, 1): the per-lane ds_read_b128 of the K operand
-//     (lane = key, 8 consecutive dims) and the ds_read_b64_tr_b16 of the V operand are both bank-conflict free, and V needs
-//     no transposed image -- the transposing read hands a lane 4 keys of one dim;
-//   * S^T = K . Q^T is ONE v_mfma_f32_16x16x32_bf16 per key tile and product (head dim 32 = one k-step), Q split per tile;
-//   * P is split in registers after the softmax; O^T = V^T . P^T takes two key tiles per MFMA (k = 32 keys: a lane's 8
-//     P values are its 4 + 4 accumulator registers of the two tiles, the V side reads the matching 4 + 4 keys);
-//   * nothing per-slot is kept in LDS (token offsets and bias codes are recomputed where needed): 160.7 KB of planes +
-//     bias column leave room for nothing else.
-// =============================================================================================
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KROWB = 64;                          // bytes per plane row: 32 bf16
-constexpr int PLANEB = FN * KROWB;                 // 25 088 B per plane (392 slots; tile 24 reads 8 rows past the end)
-constexpr int SP_TB = 0;                           // [2536] f32 bias column
-constexpr int SP_K = 2536 * 4;                     // 3 K planes
-constexpr int SP_V = SP_K + 3 * PLANEB;            // 3 V planes
-constexpr int SP_MISC = SP_V + 3 * PLANEB;         // wflag[8], gtab[25][4]
-constexpr size_t SPLIT_LDS_BYTES = SP_MISC + 8 * 4 + FNT * 4 * 4 + 512;   // + slack: tile 24 of V plane 2 reads 512 B past the planes
-static_assert(SPLIT_LDS_BYTES <= 160 * 1024, "LDS");
-static_assert((THREADS / 64) * PWS * 4 <= 3 * PLANEB, "shared-tile scratch aliases the K planes");
-
-__device__ __forceinline__ void split8v(const float (&v)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a0 = (__bf16)v[i];
-        const float r1 = v[i] - (float)a0;
-        const __bf16 a1 = (__bf16)r1;
-        const float r2 = r1 - (float)a1;
-        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
-    }
-}
-__device__ __forceinline__ void split4v(const f32x4& v, bf16x4& h0, bf16x4& h1, bf16x4& h2) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const __bf16 a0 = (__bf16)v[i];
-        const float r1 = v[i] - (float)a0;
-        const __bf16 a1 = (__bf16)r1;
-        const float r2 = r1 - (float)a1;
-        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
-    }
-}
-__device__ __forceinline__ int swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }     // pi[(row >> 2) & 3]
-
-// six products of the three-way split, smallest first
-#define MFMA6_32(acc, a, b)                                                                   \
-    do {                                                                                      \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);              \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc, 0, 0, 0);              \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);              \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);              \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);              \
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);              \
-    } while (0)
-#define MFMA6_16(acc, a, b)                                                                   \
-    do {                                                                                      \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], b[0], acc, 0, 0, 0);            \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[1], acc, 0, 0, 0);            \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[2], acc, 0, 0, 0);            \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], b[0], acc, 0, 0, 0);            \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[1], acc, 0, 0, 0);            \
-        acc = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], b[0], acc, 0, 0, 0);            \
-    } while (0)
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// The transposing read: a group of 16 lanes (one k-chunk g of the MFMA) reads a block of 4 keys x 16 dims of a V plane; lane
-// li = 4 q + pp of the group supplies the address of key row q, dims 4 pp .. 4 pp + 3, and receives dim li of the 4 keys.
-// For key rows 16 t + 4 g + q the swizzle term pi[(row >> 2) & 3] is pi[g] whatever t is, so the address is a per-lane base
-// (one per plane and 16-dim half) plus the compile-time offset 1024 t.
-__device__ __forceinline__ bf16x4 tr_read(const unsigned addr) {
-    return __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)addr));
-}
-
-template <bool SHIFTED>
-__global__ __launch_bounds__(THREADS, 2) void win_attn3d_split_kernel(
-    const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
-    const float* __restrict__ table, float* __restrict__ out, const WinParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    // Like K20 the kernel owns its CUs (all 256 architectural VGPRs x 2 waves per SIMD = the whole register file): beside
-    // its bf16 MFMA + LDS waves, v_pk_fma_f32 with an SGPR source in a neighbouring kernel's wave returned wrong values in
-    // lanes 48..63 (the dynamic mask head in the pipelined replay).
-    asm volatile("v_mov_b32 v255, 0" ::: "v255");
-    float* Tb = reinterpret_cast<float*>(smem_raw + SP_TB);
-    char* Kp = smem_raw + SP_K;
-    int* wflag = reinterpret_cast<int*>(smem_raw + SP_MISC);
-    int* gtab = wflag + 8;                                      // [25][4] key-group codes: 4 * c | region << 16
-    float* Pw = reinterpret_cast<float*>(Kp);                   // shared-tile scratch, aliases the K planes (behind a barrier)
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = blockIdx.x;
-    int qpart = 0, qsplit = 1;
-    if (bid >= p.n_main) {
-        const int rem = bid - p.n_main;
-        qsplit = p.qsplit;
-        qpart = rem % qsplit;
-        bid = p.n_main + rem / qsplit;
-    }
-    const int head = bid % p.nH; bid /= p.nH;
-    const int wx = bid % p.nww; bid /= p.nww;
-    const int wy = bid % p.nwh; bid /= p.nwh;
-    const int wz = bid % p.nwd; bid /= p.nwd;
-    const int b = bid;
-    const int C3 = 3 * p.C;
-    const int r = lane & 15, g = lane >> 4;
-    STAMP_RT(30);
-    STAMP_HWID(29);
-    STAMP(0);
-
-    // slot = col*8 + dz, col = dy*7 + dx (temporal index fastest)
-    auto slot_info = [&](int i, int& reg, int& ccode) -> int {
-        const int col = i >> 3, dz = i & 7;
-        const int dy = (col * 37) >> 8, dx = col - dy * 7;     // col / 7 for col < 64
-        const int zs = wz * 8 + dz, ys = wy * 7 + dy, xs = wx * 7 + dx;  // shifted frame
-        int z = zs + p.sd; if (z >= p.Dp) z -= p.Dp;
-        int y = ys + p.sh; if (y >= p.Hp) y -= p.Hp;
-        int x = xs + p.sw; if (x >= p.Wp) x -= p.Wp;
-        reg = (region1d(zs, p.Dp, 8, p.sd) * 3 + region1d(ys, p.Hp, 7, p.sh)) * 3 + region1d(xs, p.Wp, 7, p.sw);
-        ccode = ((dy * 13 + dx) * 15 - dz + 8) * 4;
-        return (z < p.D && y < p.H && x < p.W) ? ((b * p.D + z) * p.H + y) * p.W + x : -1;
-    };
-
-    // ---- staging: K and V rows (8 dims per thread) split into three bf16 planes each, bias column, group table
-    {
-        int differs = 0, reg0, c0;
-        (void)slot_info(0, reg0, c0);
-        constexpr int ITEMS = FN * 4;                       // (slot, 8-dim chunk)
-        constexpr int PASSES = (ITEMS + THREADS - 1) / THREADS;
-        float4 kv[PASSES][2], vv[PASSES][2];
-        int ss[PASSES];
-        const int c = tid & 3;
-#pragma unroll
-        for (int it = 0; it < PASSES; ++it) {
-            const int i = (tid + THREADS * it) >> 2;
-            int s = -2, reg = 0, cc = 0;
-            if (i < FN) {
-                s = slot_info(i, reg, cc);
-                differs |= (reg != reg0);
-            }
-            ss[it] = s;
-            if (s >= 0) {
-                const float4* row = reinterpret_cast<const float4*>(qkv + (long)s * C3 + head * HD + 8 * c);
-                kv[it][0] = row[p.C / 4]; kv[it][1] = row[p.C / 4 + 1];
-                vv[it][0] = row[p.C / 2]; vv[it][1] = row[p.C / 2 + 1];
-            } else {
-                const float4* kb = reinterpret_cast<const float4*>(qkv_bias + p.C + head * HD + 8 * c);
-                const float4* vb = reinterpret_cast<const float4*>(qkv_bias + 2 * p.C + head * HD + 8 * c);
-                kv[it][0] = kb[0]; kv[it][1] = kb[1];
-                vv[it][0] = vb[0]; vv[it][1] = vb[1];
-            }
-        }
-        constexpr int TPASS = (TBL + THREADS - 1) / THREADS;
-        float tv[TPASS];
-#pragma unroll
-        for (int it = 0; it < TPASS; ++it) {
-            const int i = it * THREADS + tid;
-            const int yx = i / 15, zz = i - yx * 15;
-            tv[it] = i < TBL ? table[(long)(zz * 169 + yx) * p.nH + head] : 0.f;
-        }
-        const int wave_differs = __any(differs);
-        if (SHIFTED && lane == 0) wflag[wave] = wave_differs ? 1 : 0;
-        STAMP(1);
-        if (tid < FNT * 4) {                                // key-group codes: group = slots 16t + 4gg .. +3
-            const int t = tid >> 2, gg = tid & 3;
-            const int col = 2 * t + (gg >> 1);
-            const int dy = (col * 37) >> 8, dx = col - dy * 7;
-            int reg = 0;
-            if (SHIFTED) {
-                const int zs = wz * 8 + 4 * (gg & 1), ys = wy * 7 + dy, xs = wx * 7 + dx;
-                reg = (region1d(zs, p.Dp, 8, p.sd) * 3 + region1d(ys, p.Hp, 7, p.sh)) * 3 + region1d(xs, p.Wp, 7, p.sw);
-            }
-            gtab[tid] = (((dy * 13 + dx) * 15 - 4 * (gg & 1) + 8) * 4) | (reg << 16);
-        }
-#pragma unroll
-        for (int it = 0; it < PASSES; ++it) {
-            const int i = (tid + THREADS * it) >> 2;
-            if (i < FN) {
-                const float kf[8] = {kv[it][0].x, kv[it][0].y, kv[it][0].z, kv[it][0].w, kv[it][1].x, kv[it][1].y, kv[it][1].z, kv[it][1].w};
-                const float vf[8] = {vv[it][0].x, vv[it][0].y, vv[it][0].z, vv[it][0].w, vv[it][1].x, vv[it][1].y, vv[it][1].z, vv[it][1].w};
-                bf16x8 h0, h1, h2;
-                char* dst = Kp + i * KROWB + ((c ^ swz(i)) << 4);
-                split8v(kf, h0, h1, h2);
-                *reinterpret_cast<bf16x8*>(dst) = h0;
-                *reinterpret_cast<bf16x8*>(dst + PLANEB) = h1;
-                *reinterpret_cast<bf16x8*>(dst + 2 * PLANEB) = h2;
-                split8v(vf, h0, h1, h2);
-                *reinterpret_cast<bf16x8*>(dst + 3 * PLANEB) = h0;
-                *reinterpret_cast<bf16x8*>(dst + 4 * PLANEB) = h1;
-                *reinterpret_cast<bf16x8*>(dst + 5 * PLANEB) = h2;
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < TPASS; ++it) {
-            const int i = it * THREADS + tid;
-            const int yx = i / 15, zz = i - yx * 15;
-            if (i < TBL) Tb[yx * 15 + 14 - zz] = tv[it] * LOG2E;
-        }
-    }
-    STAMP(2);
-    __syncthreads();
-    bool has_mask = false;
-    if (SHIFTED) {
-        int f = 0;
-#pragma unroll
-        for (int w8 = 0; w8 < THREADS / 64; ++w8) f |= wflag[w8];
-        has_mask = f != 0;
-    }
-    STAMP(3);
-    int stamp_slot = 4;
-    (void)stamp_slot;
-
-    const unsigned tbase = (unsigned)(uintptr_t)(lds_cfloat*)Tb;
-    const unsigned kaddr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)Kp;
-    const unsigned vaddr = kaddr + 3 * PLANEB;
-    // The scale lives in a vector register: as an SGPR operand of v_pk_fma_f32 it would be the form that returns wrong
-    // lanes beside waves mixing bf16 MFMAs with LDS traffic (tools/experiments/pk_mfma_probe.hip) -- this kernel's own.
-    float scale;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(scale) : "v"(0.17677669529663687f * LOG2E));
-    const int C0 = ((6 * 13 + 6) * 15 + 7) * 4;
-    // K operand of key tile t, plane pl: lane (key r, dims 8g .. 8g+7); + 1024 t
-    unsigned kfrag[3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) kfrag[pl] = kaddr + (unsigned)(pl * PLANEB + r * KROWB + ((g ^ swz(r)) << 4));
-    // V operand bases: lane li = r of group g supplies key row 4 g + (r >> 2), dims 16 dt + 4 (r & 3) ..; + 1024 t
-    unsigned vfrag[3][2];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-            const int row = 4 * g + (r >> 2), pp = r & 3;
-            vfrag[pl][dt] = vaddr + (unsigned)(pl * PLANEB + row * KROWB + (((2 * dt + (pp >> 1)) ^ swz(row)) << 4) + 8 * (pp & 1));
-        }
-    // slots 392 .. 399 of the last key tile do not exist (k-chunks g >= 2): their P is 0, but 0 x (whatever bytes follow
-    // the plane) could be NaN -- those lanes re-read tile 23 instead ("pad, don't mask": the transposing read needs every lane)
-    const unsigned last_off = (unsigned)((g >= 2 ? FNT - 2 : FNT - 1) * 16 * KROWB);
-
-    // Q fragment of a tile: lane (query r, dims 8g .. 8g+7), scaled, split; + the query's token / bias code / region
-    auto load_q = [&](int qt, float (&qf)[8], int& qsrc, int& qcode) {
-        int reg, cc;
-        const int slot = qt * 16 + r;
-        qsrc = -2; qcode = 0;
-        if (slot < FN) {
-            qsrc = slot_info(slot, reg, cc);
-            qcode = cc | (reg << 16);
-        }
-        if (qsrc >= 0) {
-            const float4* qrow = reinterpret_cast<const float4*>(qkv + (long)qsrc * C3 + head * HD + 8 * g);
-            const float4 a = qrow[0], c = qrow[1];
-            qf[0] = a.x; qf[1] = a.y; qf[2] = a.z; qf[3] = a.w; qf[4] = c.x; qf[5] = c.y; qf[6] = c.z; qf[7] = c.w;
-        } else if (qsrc == -1) {
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) qf[kk] = qkv_bias[head * HD + 8 * g + kk];
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) qf[kk] = 0.f;
-        }
-    };
-
-    // scores of key tile kt for the query fragment qs: bias gather + 6 MFMAs (+ mask)
-    auto score_tile = [&](int kt, const bf16x8 (&qs)[3], unsigned qaddr, int qreg) -> f32x4 {
-        const int gc = gtab[kt * 4 + g];
-        lds_cfloat* bp = (lds_cfloat*)(uintptr_t)(qaddr - (unsigned)(gc & 0xFFFF));
-        f32x4 a = (f32x4){bp[0], bp[1], bp[2], bp[3]};
-        bf16x8 kf[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            kf[pl] = *(const __attribute__((address_space(3))) bf16x8*)(uintptr_t)(kfrag[pl] + (unsigned)(kt * 16 * KROWB));
-        MFMA6_32(a, kf, qs);
-        if (has_mask) {
-            const float pen = ((gc >> 16) != qreg) ? -100.0f * LOG2E : 0.f;
-            a += (f32x4){pen, pen, pen, pen};
-        }
-        return a;
-    };
-
-    const bool share_last = qsplit == 1;
-    const int ntile = share_last ? FNT - 1 : FNT;
-    const int stride = (THREADS / 64) * qsplit;
-    float qn[8];
-    int qsrc_n = -2, qcode_n = 0;
-    int qt = qpart + qsplit * wave;
-    if (qt < ntile) load_q(qt, qn, qsrc_n, qcode_n);
-
-    for (; qt < ntile; qt += stride) {
-        const int qsrc = qsrc_n;
-        const unsigned qaddr = tbase + (unsigned)((qcode_n & 0xFFFF) + C0);
-        const int qreg = qcode_n >> 16;
-        bf16x8 qs[3];
-        {
-            float qf[8];
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) qf[kk] = qn[kk] * scale;
-            split8v(qf, qs[0], qs[1], qs[2]);
-        }
-        f32x4 acc[FNT];
-#pragma unroll
-        for (int t = 0; t < FNT; ++t) {
-            acc[t] = score_tile(t, qs, qaddr, qreg);
-            if (t & 1) __builtin_amdgcn_sched_barrier(0);     // two key tiles per scheduling window: the LDS reads of one
-        }                                                     // overlap the MFMAs of the other, no more fragments live
-        STAMP(stamp_slot); ++stamp_slot;
-        if (qt + stride < ntile) load_q(qt + stride, qn, qsrc_n, qcode_n);   // next tile's Q, hidden behind softmax + PV
-
-        if (g >= 2) acc[FNT - 1] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};  // slots 392..399
-        float mx = vmax3(acc[0][0], acc[0][1], acc[0][2]);
-        mx = fmaxf(mx, acc[0][3]);
-#pragma unroll
-        for (int t = 1; t < FNT; ++t) {
-            mx = vmax3(mx, acc[t][0], acc[t][1]);
-            mx = vmax3(mx, acc[t][2], acc[t][3]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        // softmax is shift-invariant; the subtraction is only needed when 2^score could leave the f32 range
-        if (!__all(fabsf(mx) < 96.f)) {
-#pragma unroll
-            for (int t = 0; t < FNT; ++t) acc[t] -= (f32x4){mx, mx, mx, mx};
-        }
-        STAMP(stamp_slot); ++stamp_slot;
-        float sum = 0.f;
-        f32x4 o0 = (f32x4){0.f, 0.f, 0.f, 0.f}, o1 = o0;
-        // exp, row sums, split of P and O^T = V^T . P^T, two key tiles (32 keys) per MFMA k-step
-#pragma unroll
-        for (int t = 0; t < FNT - 1; t += 2) {
-            float pv[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                pv[i] = __builtin_amdgcn_exp2f(acc[t][i]);
-                pv[4 + i] = __builtin_amdgcn_exp2f(acc[t + 1][i]);
-            }
-            sum += ((pv[0] + pv[1]) + (pv[2] + pv[3])) + ((pv[4] + pv[5]) + (pv[6] + pv[7]));
-            bf16x8 ps[3];
-            split8v(pv, ps[0], ps[1], ps[2]);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                bf16x8 vf[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    const bf16x4 lo = tr_read(vfrag[pl][dt] + (unsigned)(t * 16 * KROWB));
-                    const bf16x4 hi = tr_read(vfrag[pl][dt] + (unsigned)((t + 1) * 16 * KROWB));
-                    vf[pl] = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                }
-                if (dt == 0) MFMA6_32(o0, vf, ps); else MFMA6_32(o1, vf, ps);
-            }
-            __builtin_amdgcn_sched_barrier(0);                // one key-tile pair per scheduling window
-        }
-        {   // the 25th key tile alone: k = 16
-            constexpr int t = FNT - 1;
-            f32x4 pe;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pe[i] = __builtin_amdgcn_exp2f(acc[t][i]);
-            sum += (pe[0] + pe[1]) + (pe[2] + pe[3]);
-            bf16x4 ps[3];
-            split4v(pe, ps[0], ps[1], ps[2]);
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                bf16x4 vf[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) vf[pl] = tr_read(vfrag[pl][dt] + last_off);
-                if (dt == 0) MFMA6_16(o0, vf, ps); else MFMA6_16(o1, vf, ps);
-            }
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        if (qsrc >= 0) {
-            const float inv = 1.f / sum;
-            float* orow = out + (long)qsrc * p.C + head * HD + 4 * g;
-            *reinterpret_cast<float4*>(orow) = make_float4(o0[0] * inv, o0[1] * inv, o0[2] * inv, o0[3] * inv);
-            *reinterpret_cast<float4*>(orow + 16) = make_float4(o1[0] * inv, o1[1] * inv, o1[2] * inv, o1[3] * inv);
-        }
-        STAMP(stamp_slot); ++stamp_slot;
-    }
-
-    if (share_last) {
-        // the 25th query tile (8 real queries) is shared: wave w takes key tiles w, w + 8, ...; partial (O, max, sum) are
-        // merged through LDS (the scratch aliases the K planes: every wave must be done with them first)
-        constexpr int QT = FNT - 1;
-        float qf[8];
-        int qsrc, qcode;
-        load_q(QT, qf, qsrc, qcode);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) qf[kk] *= scale;
-        bf16x8 qs[3];
-        split8v(qf, qs[0], qs[1], qs[2]);
-        const unsigned qaddr = tbase + (unsigned)((qcode & 0xFFFF) + C0);
-        const int qreg = qcode >> 16;
-        constexpr int NJ = (FNT + THREADS / 64 - 1) / (THREADS / 64);
-        f32x4 a4[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int kt = wave + (THREADS / 64) * j;          // wave-uniform
-            a4[j] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (kt < FNT) {
-                f32x4 a = score_tile(kt, qs, qaddr, qreg);
-                if (kt == FNT - 1 && g >= 2) a = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                a4[j] = a;
-            }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) mx = fmaxf(fmaxf(mx, fmaxf(a4[j][0], a4[j][1])), fmaxf(a4[j][2], a4[j][3]));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        float sum = 0.f;
-        f32x4 o0 = (f32x4){0.f, 0.f, 0.f, 0.f}, o1 = o0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int kt = wave + (THREADS / 64) * j;
-            if (kt < FNT) {
-                f32x4 pe;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pe[i] = __builtin_amdgcn_exp2f(a4[j][i] - mx);
-                sum += (pe[0] + pe[1]) + (pe[2] + pe[3]);
-                bf16x4 ps[3];
-                split4v(pe, ps[0], ps[1], ps[2]);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    bf16x4 vf[3];
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl)
-                        vf[pl] = tr_read(vfrag[pl][dt] + (kt == FNT - 1 ? last_off : (unsigned)(kt * 16 * KROWB)));
-                    if (dt == 0) MFMA6_16(o0, vf, ps); else MFMA6_16(o1, vf, ps);
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        __syncthreads();                                   // every wave has finished reading the K planes
-        float* pw = Pw + wave * PWS;
-        *reinterpret_cast<float4*>(pw + r * PRS + 4 * g) = make_float4(o0[0], o0[1], o0[2], o0[3]);
-        *reinterpret_cast<float4*>(pw + r * PRS + 16 + 4 * g) = make_float4(o1[0], o1[1], o1[2], o1[3]);
-        if (g == 0) {
-            pw[16 * PRS + r] = mx;
-            pw[16 * PRS + 16 + r] = sum;
-        }
-        __syncthreads();
-        const int q = tid >> 5, d = tid & 31;
-        int osrc = -1;
-        if (q < FN - QT * 16) {
-            int reg, cc;
-            osrc = slot_info(QT * 16 + q, reg, cc);
-        }
-        if (osrc >= 0) {
-            float M = -INFINITY;
-#pragma unroll
-            for (int w8 = 0; w8 < THREADS / 64; ++w8) M = fmaxf(M, Pw[w8 * PWS + 16 * PRS + q]);
-            float num = 0.f, den = 0.f;
-#pragma unroll
-            for (int w8 = 0; w8 < THREADS / 64; ++w8) {
-                const float f = __builtin_amdgcn_exp2f(Pw[w8 * PWS + 16 * PRS + q] - M);
-                num += f * Pw[w8 * PWS + q * PRS + d];
-                den += f * Pw[w8 * PWS + 16 * PRS + 16 + q];
-            }
-            out[(long)osrc * p.C + head * HD + d] = num / den;
-        }
-    }
-    // The waves retire together: a wave that ended early would free its half of the SIMD's registers for another kernel's
-    // wave while its neighbour is still issuing MFMAs -- the co-residence the register claim at the top rules out.
-    __syncthreads();
-    STAMP(stamp_slot);
-    STAMP_RT(31);
-}
-
-// =============================================================================================
-// K1, round 6: the STREAMING form of the split kernel (what split_arith = 1 launches now).
-// Round 3's win_attn3d_split_kernel above keeps a 16-query tile's whole 16 x 400 score block in registers and does the softmax
-// between two MFMA phases; its counters say the vector ALU (40 M instructions per stage-0 launch against 7 M MFMAs) and not
-// the matrix pipe sets its time, and tools/microbench/mfma_valu_roles.hip says why: beside a stream of v_mfma_f32_16x16x32_bf16
-// a SIMD issues NO vector instruction.  tools/microbench/mfma32_valu.hip (round 6): beside v_mfma_f32_32x32x16_bf16 it does --
-// about four softmax-mix instructions per MFMA ride for free, two waves per SIMD -- if the two kinds are INTERLEAVED in the
-// instruction stream.  So:
+// K1 on the bf16 matrix cores: the STREAMING split form (what a non-zero split_arith launches on full windows).
+// The f32-input MFMA above runs at the f32 vector rate (1/16 of the bf16 matrix rate) and blocks the vector ALU while it runs;
+// this form keeps f32 semantics -- every f32 operand is split EXACTLY into three bf16 numbers (8 + 8 + 8 significant bits;
+// csrc/linear_split.hip has the arithmetic), six of the nine bf16 x bf16 products (each exact in f32) are accumulated in the f32
+// accumulators, the dropped three are <= 2^-23 |a b|.  Same window enumeration as win_attn3d_full_kernel.
+// Keeping a 16-query tile's whole 16 x 400 score block in registers and doing the softmax between two MFMA phases leaves the
+// time to the vector ALU, not to the matrix pipe (round 3: 40 M vector instructions per stage-0 launch against 7 M MFMAs,
+// DESIGN §3 K1), and tools/microbench/mfma_valu_roles.hip says why: beside a stream of v_mfma_f32_16x16x32_bf16 a SIMD issues NO
+// vector instruction.  tools/microbench/mfma32_valu.hip (round 6): beside v_mfma_f32_32x32x16_bf16 it does -- about four
+// softmax-mix instructions per MFMA ride for free, two waves per SIMD -- if the two kinds are INTERLEAVED in the instruction
+// stream.  So:
+//   * K and V of the head are split while they are staged: three planes each of [slot][32 dims] bf16 (64-B rows), 16-B chunk c
+//     of row r at chunk c ^ pi[(r >> 2) & 3], pi = (0, 3, 2, 1): the K operand of a 32-key chunk (lane = key l & 31, 16-B piece
+//     2 kk + h) and the transposing V reads (ds_read_b64_tr_b16, a 16-lane group = 4 keys x 16 dims) are both bank-conflict free
+//     on this image, and V needs no transposed copy.  Nothing per-slot is kept in LDS (token offsets and bias codes are
+//     recomputed where needed): 160.7 KB of planes + bias column leave room for nothing else.
 //   * MFMA shape 32x32x16: a wave owns a 32-query tile and walks the keys in chunks of 32.  S^T = K.Q^T of a chunk is
 //     2 k-steps x 6 products on ONE 16-register accumulator tile (lane = query l & 31, half h = l >> 5 holds keys
 //     8 j + 4 h + e of the chunk in register 4 j + e), O^T = V^T.P^T likewise 2 k-steps x 6 on one accumulator tile
@@ -1363,11 +897,34 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_split_kernel(
 //   * The bias gather needs no per-group code fetch: with the chunk's column a compile-time constant the address is a
 //     per-lane base minus a constant, i.e. the offset field of the ds_read.
 //   * 392 queries = 12 tiles of 32 + 8: waves 0..3 take two tiles, waves 4..7 (their SIMD partners) one, and the 8-query
-//     tile is shared between waves 4..7 by key chunks, merged through LDS (as the 25th tile was).
-// K / V planes, their swizzle, the bias column and the staging code are the split kernel's: the K operand of a 32-key chunk
-// (lane = key l & 31, 16-B piece 2 kk + h) and the transposing V reads (a 16-lane group = 4 keys x 16 dims) are conflict-free
-// on the same image.
+//     tile is shared between waves 4..7 by key chunks, merged through LDS (as win_attn3d_full_kernel shares its 25th).
 // =============================================================================================
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+constexpr int KROWB = 64;                          // bytes per plane row: 32 bf16
+constexpr int PLANEB = FN * KROWB;                 // 25 088 B per plane (392 slots; chunk 12's K reads run 24 rows into the next plane)
+constexpr int SP_TB = 0;                           // [2536] f32 bias column
+constexpr int SP_K = 2536 * 4;                     // 3 K planes
+constexpr int SP_V = SP_K + 3 * PLANEB;            // 3 V planes
+constexpr int SP_MISC = SP_V + 3 * PLANEB;         // wflag[8], gtab[25][4]
+constexpr size_t STREAM_LDS_BYTES = SP_MISC + 8 * 4 + FNT * 4 * 4 + 512;   // + slack behind the group table (the shared tile's row sums)
+static_assert(STREAM_LDS_BYTES <= 160 * 1024, "LDS");
+
+__device__ __forceinline__ void split8v(const float (&v)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const __bf16 a0 = (__bf16)v[i];
+        const float r1 = v[i] - (float)a0;
+        const __bf16 a1 = (__bf16)r1;
+        const float r2 = r1 - (float)a1;
+        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
+    }
+}
+__device__ __forceinline__ int swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }     // pi[(row >> 2) & 3]
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SNC = 13;                          // key chunks of 32 slots: 12 full + one with 8
 constexpr int SNQ = 13;                          // query tiles of 32: 12 full + one with 8
@@ -1461,15 +1018,14 @@ __device__ __forceinline__ bf16x8 b128_read_at(const unsigned base, const int of
     return *(const __attribute__((address_space(3))) bf16x8*)((lds_char*)(uintptr_t)base + off);
 }
 
-#ifndef SOC_K1_PF_DIST
-#define SOC_K1_PF_DIST 256                                    // workgroups ahead whose K / V rows are prefetched (same XCD, one round later)
-#endif
 template <bool SHIFTED>
 __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
     const float* __restrict__ qkv, const float* __restrict__ qkv_bias,
     const float* __restrict__ table, float* __restrict__ out, const WinParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    // owns its CUs like every bf16-MFMA kernel of the package (see win_attn3d_split_kernel)
+    // Like K20 the kernel owns its CUs (all 256 architectural VGPRs x 2 waves per SIMD = the whole register file): beside
+    // its bf16 MFMA + LDS waves, v_pk_fma_f32 with an SGPR source in a neighbouring kernel's wave returned wrong values in
+    // lanes 48..63 (the dynamic mask head in the pipelined replay).
     asm volatile("v_mov_b32 v255, 0" ::: "v255");
     float* Tb = reinterpret_cast<float*>(smem_raw + SP_TB);
     char* Kp = smem_raw + SP_K;
@@ -1494,13 +1050,6 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
     const int wz = bid % p.nwd; bid /= p.nwd;
     const int b = bid;
     const int C3 = 3 * p.C;
-#ifdef SOC_K1_STAGGER                                         // diagnostic: the first round of workgroups starts spread over
-    if (blockIdx.x < 256) {                                   // 8 steps of SOC_K1_STAGGER cycles (are the K / V bursts of a round in lockstep?)
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        const unsigned long long wait = (unsigned long long)((blockIdx.x >> 3) & 7) * SOC_K1_STAGGER;
-        while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
     STAMP_RT(30);
     STAMP_HWID(29);
     STAMP(0);
@@ -1566,7 +1115,7 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
     if (qt < qend) load_q(qt, q_first, qsrc_first, qcode_first);
     if (light) load_q(SNQ - 1, q_shared, qsrc_shared, qcode_shared);
 
-    // ---- staging (the split kernel's): K and V rows (8 dims per thread) split into three bf16 planes each, bias column, group table
+    // ---- staging: K and V rows (8 dims per thread) split into three bf16 planes each, bias column, group table
     {
         int differs = 0, reg0, c0;
         (void)slot_info(0, reg0, c0);
@@ -1594,17 +1143,11 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
 #pragma unroll
         for (int it = 0; it < PASSES; ++it) {
             const int s = s_pass[it];
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 16)         // diagnostic: no K / V row loads
-            if (s >= 0) {
-                kv[it][0] = kv[it][1] = vv[it][0] = vv[it][1] = make_float4(0.01f * c, 0.02f, 0.03f * s, 0.04f);
-            } else {
-#else
             if (s >= 0) {
                 const float4* row = reinterpret_cast<const float4*>(qkv + (long)s * C3 + head * HD + 8 * c);
                 kv[it][0] = row[p.C / 4]; kv[it][1] = row[p.C / 4 + 1];
                 vv[it][0] = row[p.C / 2]; vv[it][1] = row[p.C / 2 + 1];
             } else {
-#endif
                 const float4* kb = reinterpret_cast<const float4*>(qkv_bias + p.C + head * HD + 8 * c);
                 const float4* vb = reinterpret_cast<const float4*>(qkv_bias + 2 * p.C + head * HD + 8 * c);
                 kv[it][0] = kb[0]; kv[it][1] = kb[1];
@@ -1616,16 +1159,12 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
 #pragma unroll
         // The bias column of this head, walked in the TABLE's order (entry r = zz * 169 + yx at table[r * nH + head]: the 64 lanes of
         // a load touch 64 * nH floats, 6 cache lines at nH = 3, instead of one line each) and transposed by the LDS store below
-        // (stride 15 words: no bank conflicts).  Measured against the split kernel's walk in the LDS layout's order, same box:
+        // (stride 15 words: no bank conflicts).  Measured against a walk in the LDS layout's order, same box:
         // 1 151 -> 1 148 / 1 202 -> 1 198 us at ten clips per launch -- the gather's cost is its five load instructions in the
         // queue behind the K / V rows (a build without it: -5 %), not the lines it touches.
         for (int it = 0; it < TPASS; ++it) {
             const int r = it * THREADS + tid;
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 8)          // diagnostic: no bias-table gather
-            tv[it] = 0.f;
-#else
             tv[it] = r < TBL ? table[(long)r * p.nH + head] : 0.f;
-#endif
         }
         const int wave_differs = __any(differs);
         if (SHIFTED && lane == 0) wflag[wave] = wave_differs ? 1 : 0;
@@ -1649,10 +1188,6 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
                 const float vf[8] = {vv[it][0].x, vv[it][0].y, vv[it][0].z, vv[it][0].w, vv[it][1].x, vv[it][1].y, vv[it][1].z, vv[it][1].w};
                 bf16x8 h0, h1, h2;
                 char* dst = Kp + i * KROWB + ((c ^ swz(i)) << 4);
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 32)         // diagnostic: no operand split, one LDS store per item
-                *reinterpret_cast<float4*>(dst) = make_float4(kf[0] + vf[1], kf[2], vf[3], kf[4]);
-                continue;
-#endif
                 split8v(kf, h0, h1, h2);
                 *reinterpret_cast<bf16x8*>(dst) = h0;
                 *reinterpret_cast<bf16x8*>(dst + PLANEB) = h1;
@@ -1683,41 +1218,6 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
     int stamp_slot = 4;
     (void)stamp_slot;
 
-#ifdef SOC_K1_PREFETCH                                          // diagnostic, measured a LOSS (1 148 -> 1 186 us at ten clips, stage 0)
-    // ---- the K / V rows of the workgroup that follows this one on this XCD (workgroup b runs on XCD b % 8: b + 256 is the one a
-    //      round later) are pulled into the XCD's L2 while this workgroup computes: staging is bound by the latency of its 784 row
-    //      reads (12.5 k cycles of a 68 k-cycle workgroup at launch-group sizes, where qkv no longer sits in the MALL), not by any
-    //      bandwidth.  One dword per 128-B row through the LDS-DMA path (no destination register to keep alive), into a dummy
-    //      LDS word per lane that nothing reads.
-    {
-        __shared__ int pf_sink[64];
-        int nb = (int)blockIdx.x + SOC_K1_PF_DIST;
-        if (nb < (int)gridDim.x && tid < FN) {
-            if (nb >= p.n_main) nb = p.n_main + (nb - p.n_main) / p.qsplit;
-            const int head2 = nb % p.nH; nb /= p.nH;
-            const int wx2 = nb % p.nww; nb /= p.nww;
-            const int wy2 = nb % p.nwh; nb /= p.nwh;
-            const int wz2 = nb % p.nwd; nb /= p.nwd;
-            const int col = tid >> 3, dz = tid & 7;
-            const int dy = (col * 37) >> 8, dx = col - dy * 7;
-            int z = wz2 * 8 + dz + p.sd; if (z >= p.Dp) z -= p.Dp;
-            int y = wy2 * 7 + dy + p.sh; if (y >= p.Hp) y -= p.Hp;
-            int x = wx2 * 7 + dx + p.sw; if (x >= p.Wp) x -= p.Wp;
-            if (z < p.D && y < p.H && x < p.W) {
-                const float* row = qkv + (long)(((nb * p.D + z) * p.H + y) * p.W + x) * C3 + head2 * HD;
-                // inline asm, not __builtin_amdgcn_global_load_lds: hipcc would put s_waitcnt vmcnt(0) in front of the first
-                // ds_read_b64_tr_b16 that follows (an LDS access it cannot tell from the sink) -- a stall of one HBM latency per
-                // workgroup.  Untracked, the two loads only make later vmcnt waits conservative (returns are in order).
-                const unsigned sink = (unsigned)(uintptr_t)(__attribute__((address_space(3))) int*)pf_sink;
-                unsigned m0_saved;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-                             "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(m0_saved) : "v"(row + p.C), "v"(row + 2 * p.C), "s"(sink));
-            }
-        }
-    }
-#endif
-
     const unsigned tbase = (unsigned)(uintptr_t)(lds_cfloat*)Tb;
     const unsigned kaddr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)Kp;
     const unsigned vaddr = kaddr + 3 * PLANEB;
@@ -1747,15 +1247,9 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
         }
     }
     auto k_read = [&](int pl, int kk, int off) -> bf16x8 {            // K fragment of plane pl, k-step kk at byte offset off
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 2)          // diagnostic: no LDS reads of K / V fragments
-        return __builtin_bit_cast(bf16x8, (u32x4){kb01[kk] + (unsigned)off, kb2[kk], 0x3f803f80u, (unsigned)pl});
-#endif
         return pl == 2 ? b128_read_at(kb2[kk], off) : b128_read_at(kb01[kk], pl * PLANEB + off);
     };
     auto v_read = [&](int pl, int jj, int off) -> bf16x4 {            // V key quartet jj of plane pl at byte offset off
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 2)
-        return __builtin_bit_cast(bf16x4, (f32x2){__builtin_bit_cast(float, vb01[jj] + (unsigned)off), __builtin_bit_cast(float, 0x3f803f80u + (unsigned)pl)});
-#endif
         return pl == 2 ? tr_read_at(vb2[jj], off) : tr_read_at(vb01[jj], pl * PLANEB + off);
     };
 
@@ -1825,10 +1319,6 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
         // slot k of a phase: segment k % 3 of pair k / 3 of the 8 scores s[8 half ..]; pairs >= npairs are keys that do not exist
         // (P = 0); nprev = pairs of the phase before (0: none), whose last one is finished in slot 0
         auto soft_slot = [&](const f32x16& s, int half, int k, int npairs, u32x4 (&P)[3], u32x4 (&Pprev)[3], int nprev) {
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 1)          // diagnostic (tools/k1_probe.py --flags): no vector work in the tile
-            if (k == 0) { P[0] = (u32x4){0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u}; P[1] = P[0]; P[2] = P[0]; sum += s[half]; }
-            return;
-#endif
             const int i = k / 3, seg = k % 3;
             if (seg == 0) {
                 if (i == 0 && nprev > 0) finish(Pprev, nprev - 1);
@@ -1841,19 +1331,11 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
             }
         };
         auto mf_pv = [&](int k, const bf16x4 (&lo)[3], const bf16x4 (&hi)[3], const u32x4 (&P)[3]) {
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 4)          // diagnostic: no MFMAs (the operands are still consumed)
-            if (k == 5) O[0] += (float)lo[0][0] + (float)hi[1][0] + (float)lo[2][1] + __builtin_bit_cast(float, P[0][0] ^ P[1][1] ^ P[2][2]);
-            return;
-#endif
             const bf16x4 l = lo[PA[k]], h = hi[PA[k]];
             const bf16x8 vf = {l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]};
             O = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8, P[PB[k]]), O, 0, 0, 0);
         };
         auto mf_qk = [&](int k, f32x16& s, const bf16x8 (&kfr)[3], int kk) {
-#if defined(SOC_K1_VAR) && (SOC_K1_VAR & 4)
-            if (k == 5) s[kk] += (float)kfr[0][0] + (float)kfr[1][1] + (float)kfr[2][2];
-            return;
-#endif
             s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[PA[k]], qs[kk][PB[k]], s, 0, 0, 0);
         };
         // bias of key column j of chunk c into scores 4 j .. 4 j + 3 (+ the shift-mask penalty)
@@ -2120,23 +1602,11 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
             float tot = sum + __shfl_xor(sum, 32);
             // 2^score without a max is legal iff the row sum says so (NaN fails the test too); lanes of queries that do not exist
             // (the 24 surplus lanes of tile 12 in a split pair: Q = 0, and with a shift mask possibly every key masked) do not vote
-#if (defined(SOC_K1_DBG) && (SOC_K1_DBG == 1 || SOC_K1_DBG >= 3)) || defined(SOC_K1_VAR)
-            if (false) {
-#elif defined(SOC_K1_DBG) && SOC_K1_DBG == 2
-            if (true) {
-#else
             if (!__all(qsrc == -2 || (tot > 0x1p-60f && tot < 0x1p60f))) {
-#endif
                 sum = slow_tile(qs, qb, qreg, O);
                 tot = sum + __shfl_xor(sum, 32);
             }
-#if defined(SOC_K1_DBG) && SOC_K1_DBG == 3       // raw O, no normalisation
-            store_tile(qsrc, O, 1.0f);
-#elif defined(SOC_K1_DBG) && SOC_K1_DBG == 4     // the row sum in every dim
-            { f32x16 T; for (int i = 0; i < 16; ++i) T[i] = tot; store_tile(qsrc, T, 1.0f); }
-#else
             store_tile(qsrc, O, tot);
-#endif
             if (more) split_q(carry, qs);
             STAMP(stamp_slot); ++stamp_slot;
         }
@@ -2154,9 +1624,6 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
             const float tq = (xsum[q] + xsum[8 + q]) + (xsum[16 + q] + xsum[24 + q]);
             legal = legal && tq > 0x1p-60f && tq < 0x1p60f;             // (NaN fails too)
         }
-#ifdef SOC_K1_VAR
-        legal = true;
-#endif
         if (!legal) {                                      // block-uniform: every thread read the same 32 words
             if (light) shared_partial(true);
             __syncthreads();                               // ... and now every wave is done with the K planes
@@ -2191,79 +1658,32 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
             }
         }
     }
-    // The waves retire together (the co-residence rule of the bf16-MFMA kernels).
+    // The waves retire together: a wave that ended early would free its half of the SIMD's registers for another kernel's
+    // wave while its neighbour is still issuing MFMAs -- the co-residence the register claim at the top rules out.
     __syncthreads();
     STAMP(stamp_slot);
     STAMP_RT(31);
 }
 
-int launch_full(const float* qkv, const float* qkv_bias, const float* table, float* out,
-                const WinParams& p, long blocks, hipStream_t st) {
-    const size_t lds = FULL_LDS_BYTES;
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];   // per device: the attribute is device state
+// One launcher for every form: a <false> / <true> (shifted) kernel pair, each instantiation with its own per-device flag (the
+// dynamic-LDS attribute is device state, and a flag shared by two pairs would leave the second pair's attribute unset).
+typedef void (*WinKernel)(const float*, const float*, const float*, float*, const WinParams);
+template <WinKernel K_PLAIN, WinKernel K_SHIFTED>
+int launch_pair(const float* qkv, const float* qkv_bias, const float* table, float* out,
+                const WinParams& p, long blocks, size_t lds, hipStream_t st) {
+    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
     const int dev = soc_current_device();
     if (dev < 0) return SOC_ELAUNCH;
     if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_full_kernel<false>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(K_PLAIN),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_full_kernel<true>),
+            hipFuncSetAttribute(reinterpret_cast<const void*>(K_SHIFTED),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return SOC_ELAUNCH;
         attr_set[dev].store(true, std::memory_order_release);   // idempotent: a racing thread just sets it again
     }
-    if (p.shifted)
-        hipLaunchKernelGGL((win_attn3d_full_kernel<true>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
-    else
-        hipLaunchKernelGGL((win_attn3d_full_kernel<false>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
-    return soc_check_launch();
-}
-
-int launch_split(const float* qkv, const float* qkv_bias, const float* table, float* out,
-                 const WinParams& p, long blocks, hipStream_t st) {
-    const size_t lds = SPLIT_LDS_BYTES;
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_split_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_split_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    if (p.shifted)
-        hipLaunchKernelGGL((win_attn3d_split_kernel<true>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
-    else
-        hipLaunchKernelGGL((win_attn3d_split_kernel<false>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
-    return soc_check_launch();
-}
-
-int launch_stream(const float* qkv, const float* qkv_bias, const float* table, float* out,
-                  const WinParams& p, long blocks, hipStream_t st) {
-    const size_t lds = SPLIT_LDS_BYTES;                        // + 256 B static (the prefetch sink)
-    static_assert(SPLIT_LDS_BYTES + 256 <= 160 * 1024, "LDS");
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_stream_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_stream_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess)
-            return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    if (p.shifted)
-        hipLaunchKernelGGL((win_attn3d_stream_kernel<true>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
-    else
-        hipLaunchKernelGGL((win_attn3d_stream_kernel<false>), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv,
-                           qkv_bias, table, out, p);
+    hipLaunchKernelGGL((p.shifted ? K_SHIFTED : K_PLAIN), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv, qkv_bias,
+                       table, out, p);
     return soc_check_launch();
 }
 
@@ -2273,24 +1693,8 @@ int launch_nt(const float* qkv, const float* qkv_bias, const float* table, float
     const size_t lds = (size_t)(2 * NT * 16 * RS + ((p.table_len + 3) & ~3)) * sizeof(float) +
                        (3 * NT * 16 + 8) * sizeof(int);
     if (lds > 160 * 1024) return SOC_EUNSUPPORTED;
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];   // per instantiation and per device
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_kernel<NT, NT_PREV, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(win_attn3d_kernel<NT, NT_PREV, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    if (p.shifted)
-        hipLaunchKernelGGL((win_attn3d_kernel<NT, NT_PREV, true>), dim3((unsigned)blocks), dim3(THREADS), lds, st,
-                           qkv, qkv_bias, table, out, p);
-    else
-        hipLaunchKernelGGL((win_attn3d_kernel<NT, NT_PREV, false>), dim3((unsigned)blocks), dim3(THREADS), lds, st,
-                           qkv, qkv_bias, table, out, p);
-    return soc_check_launch();
+    return launch_pair<win_attn3d_kernel<NT, NT_PREV, false>, win_attn3d_kernel<NT, NT_PREV, true>>(
+        qkv, qkv_bias, table, out, p, blocks, lds, st);
 }
 
 int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
@@ -2311,8 +1715,6 @@ struct Plan { int n_main, qsplit; };
 
 struct CostModel { double sigma, share; };
 constexpr CostModel COST_F32{0.86, 0.27};
-// split kernel: a tile-slot is ~2.6x shorter, staging (global-load latency + the operand split) is not
-constexpr CostModel COST_SPLIT{2.3, 0.6};
 // streaming kernel (round 6): the unit is one 32-query tile on one SIMD (13 chunks, ~11 k cycles); an unsplit workgroup is
 // staging + 3 tiles per SIMD + the shared 8-query tile
 constexpr CostModel COST_STREAM{0.9, 0.3};        // stamps (tools/k1_probe.py --stamps): staging 14.6 k cycles, 3 tiles per SIMD ~50 k, tail ~5 k
@@ -2344,11 +1746,11 @@ double simulate_tail(long pairs, int NT, int cus, int n_main, int q, bool shared
     return makespan + 1e-4 * (double)(n_main + (pairs - n_main) * q);
 }
 
-Plan plan_schedule(long pairs, int NT, int cus, bool shared_last, int split) {      // split: 0 f32 form, 1 streaming, 2 round-3 split form
+Plan plan_schedule(long pairs, int NT, int cus, bool shared_last, bool split) {      // split: the streaming form, else f32
     static std::mutex mu;
-    static std::map<std::tuple<long, int, int, bool, int>, Plan> cache;     // one entry per launch geometry
+    static std::map<std::tuple<long, int, int, bool, bool>, Plan> cache;     // one entry per launch geometry
     const auto key = std::make_tuple(pairs, NT, cus, shared_last, split);
-    const CostModel& cm = split == 1 ? COST_STREAM : split == 2 ? COST_SPLIT : COST_F32;
+    const CostModel& cm = split ? COST_STREAM : COST_F32;
     {
         std::lock_guard<std::mutex> lk(mu);
         auto it = cache.find(key);
@@ -2409,10 +1811,10 @@ extern "C" int soc_win_attn3d_f32(const float* qkv, const float* qkv_bias, const
     if ((long)B * D * H * W * 3 * C >= (1L << 31)) return SOC_EUNSUPPORTED;  // int token offsets
     const long pairs = (long)B * p.nwd * p.nwh * p.nww * n_heads;
     const bool full_window = win_d == 8 && win_h == 7 && win_w == 7 && tab_d == 8 && tab_h == 7 && tab_w == 7;
-    // full 8x7x7 windows only; a launch argument, not process state: 1 = the streaming form (round 6), 2 = the round-3 split form
-    const int split = !full_window ? 0 : split_arith == 2 ? 2 : split_arith != 0 ? 1 : 0;
+    // the streaming bf16-split form: full 8x7x7 windows only; a launch argument, not process state
+    const bool split = full_window && split_arith != 0;
     {
-        const Plan pl = plan_schedule(pairs, split == 1 ? SNQ : p.NT, num_cus((hipStream_t)stream), full_window, split);
+        const Plan pl = plan_schedule(pairs, split ? SNQ : p.NT, num_cus((hipStream_t)stream), full_window, split);
         p.n_main = pl.n_main;
         p.qsplit = pl.qsplit;
     }
@@ -2427,12 +1829,12 @@ extern "C" int soc_win_attn3d_f32(const float* qkv, const float* qkv_bias, const
     hipStream_t st = (hipStream_t)stream;
     // key/query tiles are a compile-time constant (fully unrolled MFMA schedule); a window with
     // fewer tokens runs on the next larger instantiation with the surplus keys masked out.
-    if (split == 1)
-        return launch_stream(qkv, qkv_bias, bias_table, out, p, blocks, st);
-    if (split == 2)
-        return launch_split(qkv, qkv_bias, bias_table, out, p, blocks, st);
+    if (split)
+        return launch_pair<win_attn3d_stream_kernel<false>, win_attn3d_stream_kernel<true>>(
+            qkv, qkv_bias, bias_table, out, p, blocks, STREAM_LDS_BYTES, st);
     if (full_window)
-        return launch_full(qkv, qkv_bias, bias_table, out, p, blocks, st);
+        return launch_pair<win_attn3d_full_kernel<false>, win_attn3d_full_kernel<true>>(
+            qkv, qkv_bias, bias_table, out, p, blocks, FULL_LDS_BYTES, st);
     if (p.NT <= 7) return launch_nt<7, 0>(qkv, qkv_bias, bias_table, out, p, blocks, st);
     if (p.NT <= 10) return launch_nt<10, 7>(qkv, qkv_bias, bias_table, out, p, blocks, st);
     if (p.NT <= 13) return launch_nt<13, 10>(qkv, qkv_bias, bias_table, out, p, blocks, st);

@@ -383,11 +383,9 @@ def clamp_window(size: Sequence[int], window: Sequence[int], shift: Sequence[int
 
 
 def _k1_form() -> int:
-    """The `split_arith` launch argument of K1: 0 = f32-input MFMA, 1 = the bf16-split STREAMING form (round 6: 32-query tiles,
-    key chunks of 32, softmax between the MFMAs), 2 = round 3's split form (SOC_K1_FORM=r3: kept for A/B runs and its tests)."""
-    if not k1_split_enabled():
-        return 0
-    return 2 if _os.environ.get("SOC_K1_FORM", "") == "r3" else 1
+    """The `split_arith` launch argument of K1: 0 = f32-input MFMA, 1 = the bf16-split STREAMING form (32-query tiles, key
+    chunks of 32, softmax between the MFMAs)."""
+    return 1 if k1_split_enabled() else 0
 
 
 def window_attention3d(qkv: Tensor, qkv_bias: Tensor, bias_table: Tensor, n_heads: int,
@@ -844,7 +842,6 @@ def ws_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, ln: Opti
 
 # ---------------------------------------------------------------------------------------------
 # K20: f32 linear layers on the bf16 matrix cores by exact operand splitting
-import os as _os
 
 # The arithmetic mode of a forward and the routing rules that hang on it live in matmul_mode.py, the cache of packed weight images
 # in derived_cache.py; both are re-exported here (callers and tests use hot_ops.<name>).

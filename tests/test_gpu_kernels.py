@@ -179,20 +179,6 @@ def test_window_attention_streaming_form_takes_its_max_path_per_tile(ops, where)
         assert bool(torch.isfinite(out).all())
 
 
-def test_window_attention_streaming_and_round3_forms_agree(ops, monkeypatch):
-    """split_arith = 1 (streaming, round 6) and 2 (round 3's split form, SOC_K1_FORM=r3) are the same arithmetic in another order:
-    stage-2 geometry (whole pairs + pairs split over query tiles), shifted, to f32 rounding."""
-    g = torch.Generator().manual_seed(9)
-    qkv = torch.randn(1, 8, 23, 40, 3 * 384, generator=g)
-    bias = torch.randn(3 * 384, generator=g) * 0.5
-    table = torch.randn(2535, 12, generator=g) * 0.5
-    monkeypatch.delenv("SOC_K1_FORM", raising=False)
-    a = ops.window_attention3d(dev(qkv), dev(bias), dev(table), 12, O.WINDOW, (4, 3, 3))
-    monkeypatch.setenv("SOC_K1_FORM", "r3")
-    b = ops.window_attention3d(dev(qkv), dev(bias), dev(table), 12, O.WINDOW, (4, 3, 3))
-    assert maxdiff(a, b.cpu()) < 3e-6 * max(1.0, float(b.abs().max()))
-
-
 def test_window_attention_batch_gt1(ops):
     d, scale = _win_case(ops, 2, 8, 9, 15, 2, (4, 3, 3), seed=5)
     assert d < 2e-5 * max(scale, 1.0)

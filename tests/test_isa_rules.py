@@ -141,14 +141,15 @@ def test_no_scratch_inside_the_mfma_stream(unit):
             # K1's streaming form (round 6) has no LDS-DMA ring; its MFMAs come in three places (the shared tile's chunks, the
             # unrolled tile, the two-pass tile) with the tile loop's entry and exit between them, where a few values that live
             # ACROSS the loop (the shared tile's partial row sum, lane ids) may pass through scratch.  Inside a run of MFMAs --
-            # the unrolled tile is ~300 of them within ~4 500 lines -- nothing may.
+            # the unrolled tile is ~300 of them within ~4 500 lines -- nothing may.  What it has today: the shifted form 16 B
+            # (four scratch_ instructions, all between runs of MFMAs), the unshifted form none; more is a regression.
             lines = body.splitlines()
             mf = [i for i, ln in enumerate(lines) if BF16_MFMA_ISA.search(ln)]
             for i, ln in enumerate(lines):
                 if "scratch_" in ln:
                     near = sum(1 for j in mf if abs(j - i) <= 200)
                     assert near <= 12, (src, name, i, ln.strip(), near)      # (a slot of the unrolled tile is ~9 lines: 200 lines of it hold ~45 MFMAs)
-            assert meta[name]["private_segment_fixed_size"] <= 160, (src, name, meta[name])
+            assert meta[name]["private_segment_fixed_size"] <= (16 if "ILb1E" in name else 0), (src, name, meta[name])
             continue
         assert "scratch_" not in body[ms[0]:ms[-1]], (src, name)
         # behind the last MFMA (the epilogue of a range, inside the span loop): nothing either, except K24's GELU epilogue at

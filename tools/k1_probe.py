@@ -3,6 +3,8 @@
 s_memrealtime at start / end: in-kernel clock under load, per-phase cycles, workgroup rounds per CU.
 (C) --sweep: forced schedules.  (D) --insitu: forced schedules timed inside the 12-launch sequence of a forward (every
 launch on its own qkv tensor, 634 MB in all, so that K/V staging sees the cache state it has inside the model).
+--flags: extra -D options of the probe's own build of win_attn3d.hip.  K1_SPLIT (default 1): the `split_arith` argument,
+1 = the streaming bf16-split form, 0 = the f32 form.
 usage: python tools/k1_probe.py [--stamps|--sweep|--insitu] [--flags=-DX,-DY] [stages...]"""
 import ctypes as C
 import os

@@ -30,9 +30,8 @@ traffic)
   python3 tools/pmc_traffic.py $(ls $P/pmc_fetch/*/*counter_collection.csv | head -1) $(ls $P/pmc_write/*/*counter_collection.csv | head -1) $GROUP > $P/r06_hbm_traffic_pmc.json
   ;;
 counters)
-  # ---- (c) K1 (streaming form, and the round-3 split form beside it) at the shapes of one clip and of a launch group
-  for form in stream r3; do
-    if [ $form = r3 ]; then export SOC_K1_FORM=r3; else unset SOC_K1_FORM; fi
+  # ---- (c) K1 (streaming form) at the shapes of one clip and of a launch group
+  for form in stream; do
     for clips in 1 $GROUP; do
       for site in k1s0 k1s2; do
         tag=${site}_${form}_x${clips}
@@ -42,12 +41,11 @@ counters)
       done
     done
   done
-  unset SOC_K1_FORM
   python3 - <<'PY' > gpurun_out/r06/r06_k1_pmc.json
 import glob, json
 out = {"command": "tools/pmc_run_r06.sh counters: rocprofv3 --kernel-trace --pmc <8 SQ counters> | <LDS / co-execution counters, GRBM_GUI_ACTIVE> "
                   "(two separate passes) -- python3 tools/run_kernel.py k1s<stage> 12 <clips per launch>; tools/pmc_agg.py: mean per launch.  "
-                  "stream = win_attn3d_stream_kernel (round 6, split_arith 1), r3 = win_attn3d_split_kernel (round 3, SOC_K1_FORM=r3).  "
+                  "stream = win_attn3d_stream_kernel (round 6, split_arith 1).  "
                   "matrix_pipe_busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE x 128)", "counters": {}}
 for f in sorted(glob.glob("gpurun_out/r06/k1s*_counters.json")):
     d = json.load(open(f))
