@@ -540,6 +540,33 @@ int soc_linear_split_f32(const float* x, const float* x_add, const float* row_st
                          const void* w_packed, const float* bias, const float* residual, const float* mul, float* out,
                          float* out2, int n_split, long M, int N, int K, int act, int tile_cfg, void* stream);
 
+/*
+ * K27 -- the per-pixel part of the DAVIS J&F evaluation, on label maps that are already on the device (the output of K6's
+ * DAVIS form).  Replaces, for every (ground-truth object i, predicted object j, frame t), the array work of
+ *   db_eval_iou                                  davis2017/metrics.py:6-37
+ *   f_measure with _seg2bmap and the disk dilation  davis2017/metrics.py:57-119, :122-178 (equal-size case)
+ *   and the loops over objects / proposals / frames of davis2017/evaluation.py:28-41 (pairs = 0), :44-58 (pairs = 1)
+ * by six integers, from which the host forms J and F in f64 with the reference's own expressions:
+ *   counts[..., 0] inter    = sum(fg & gt & ~void)       counts[..., 1] union    = sum((fg | gt) & ~void)
+ *   counts[..., 2] n_fg     = sum(fb)                    counts[..., 3] n_gt     = sum(gb)
+ *   counts[..., 4] fg_match = sum(fb & dil(gb))          counts[..., 5] gt_match = sum(gb & dil(fb))
+ * with gt = (gt_labels == i), fg = (pred_labels == j), void = use_void && (gt_labels == 255), fb / gb = _seg2bmap of
+ * fg / gt & ~void, and dil the dilation by the disk of `radius` pixels (dx^2 + dy^2 <= radius^2; pixels outside the image
+ * never contribute) -- cv2.dilate(b, skimage.morphology.disk(radius)) on a binary image.
+ *   gt_labels, pred_labels [T, H, W] uint8 (0 = background; 255 in gt_labels = void when use_void != 0)
+ *   pairs != 0: counts [G, P, T, 6] int32, object i + 1 against proposal j + 1 for every pair (task "unsupervised")
+ *   pairs == 0: counts [G, T, 6]    int32, object k + 1 against prediction k + 1; predictions k >= P are empty masks
+ *               (task "semi-supervised")
+ * workspace: the bytes the query below returns, device memory (the one-bit-per-pixel planes of a chunk of frames).
+ * Decided from the sizes before any launch: null pointer or T, H, W <= 0 -> SOC_EINVAL; radius outside [0, 64], G or P
+ * outside [0, 255], G = P = 0, H * W >= 2^31 -> SOC_EUNSUPPORTED; a short workspace -> SOC_EWORKSPACE.  The query returns 0
+ * for sizes the launch refuses.  Integer arithmetic only: the result does not depend on the launch geometry or the run.
+ */
+size_t soc_davis_jf_workspace_bytes(int G, int P, int T, int H, int W);
+int soc_davis_jf_counts_u8(const uint8_t* gt_labels, const uint8_t* pred_labels, int32_t* counts, int G, int P, int T, int H,
+                           int W, int radius, int use_void, int pairs, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

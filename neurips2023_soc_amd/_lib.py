@@ -24,9 +24,12 @@ EXPORTS = ("soc_hip_abi_version", "soc_hip_error_string", "soc_stream_cus", "soc
            "soc_mlp_split_packed_bytes", "soc_mlp_split_pack_f32",
            "soc_mlp_split_workspace_bytes", "soc_mlp_split_plan", "soc_mlp_split_max_hidden", "soc_mlp_split_f32", "soc_mlp_split_variant_f32",
            "soc_xs_linear_packed_bytes", "soc_xs_linear_pack_f32", "soc_xs_linear_plan", "soc_xs_linear_f32",
-           "soc_small_attn_f32", "soc_select_pack_f32")
+           "soc_small_attn_f32", "soc_select_pack_f32",
+           "soc_davis_jf_workspace_bytes", "soc_davis_jf_counts_u8")
 ABI_VERSION = 16
+SOC_EINVAL = -1            # include/soc_hip.h: null pointer / non-positive dimension
 SOC_EUNSUPPORTED = -2      # include/soc_hip.h: shape outside what the kernel is built for
+SOC_EWORKSPACE = -4        # include/soc_hip.h: workspace too small
 
 _lib = None
 
@@ -154,6 +157,10 @@ def load() -> C.CDLL:
     lib.soc_linear_split_f32.argtypes = [p] * 10 + [i, C.c_long, i, i, i, i, p]
     lib.soc_small_attn_f32.restype = i
     lib.soc_small_attn_f32.argtypes = [p, p, p, p, p, i, i, i, i, f, C.c_long, C.c_long, p]
+    lib.soc_davis_jf_workspace_bytes.restype = C.c_size_t
+    lib.soc_davis_jf_workspace_bytes.argtypes = [i] * 5
+    lib.soc_davis_jf_counts_u8.restype = i
+    lib.soc_davis_jf_counts_u8.argtypes = [p, p, p] + [i] * 8 + [p, C.c_size_t, p]
     if lib.soc_hip_abi_version() != ABI_VERSION:
         raise SocHipError("libsoc_hip.so ABI version mismatch; rebuild it")
     _lib = lib

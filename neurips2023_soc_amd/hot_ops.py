@@ -659,6 +659,30 @@ def upsample_merge_labels(mask_logits: Tensor, size: Sequence[int], threshold: f
     return out
 
 
+def davis_jf_counts(gt_labels: Tensor, pred_labels: Tensor, G: int, P: int, radius: int, use_void: bool = True,
+                    pairs: bool = True) -> Tensor:
+    """K27.  gt_labels, pred_labels [T,H,W] uint8 label maps (0 = background, 255 in gt = void when use_void) -> int32 counts
+    (inter, union, n_fg, n_gt, fg_match, gt_match) of the DAVIS J and F measures: [G,P,T,6] for every (object, proposal) pair,
+    or [G,T,6] (pairs=False) for object k against prediction k.  davis_eval.jf_from_counts turns them into J and F."""
+    _need_gpu(gt_labels, pred_labels)
+    lib = _lib.load()
+    if (gt_labels.dtype != torch.uint8 or pred_labels.dtype != torch.uint8 or gt_labels.dim() != 3
+            or gt_labels.shape != pred_labels.shape):
+        raise _lib.SocHipError("davis_jf_counts: gt_labels and pred_labels must be uint8 [T,H,W] of one shape")
+    gt_labels, pred_labels = gt_labels.contiguous(), pred_labels.contiguous()
+    T, H, W = gt_labels.shape
+    G, P = int(G), int(P)
+    out = torch.empty((G, P, T, 6) if pairs else (G, T, 6), dtype=torch.int32, device=gt_labels.device)
+    need = lib.soc_davis_jf_workspace_bytes(G, P, T, H, W)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=gt_labels.device)
+    counts = out if out.numel() else torch.empty(1, dtype=torch.int32, device=gt_labels.device)
+    with _timed("davis_jf_counts", 2 * gt_labels.numel() + out.numel() * 4):
+        code = lib.soc_davis_jf_counts_u8(gt_labels.data_ptr(), pred_labels.data_ptr(), counts.data_ptr(), G, P, T, H, W,
+                                          int(radius), int(bool(use_void)), int(bool(pairs)), ws.data_ptr(), need, _stream())
+    _lib.check(code, "soc_davis_jf_counts_u8")
+    return out
+
+
 def resize_normalize(frames: Tensor, size: Sequence[int], tables_x, tables_y, mean: Sequence[float],
                      std: Sequence[float], return_u8: bool = False):
     """K9.  frames [T,H0,W0,3] uint8 -> [T,3,h,w] float32 = Normalize(ToTensor(PIL bilinear resize)).

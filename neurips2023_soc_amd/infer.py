@@ -268,6 +268,8 @@ def _run_dataset(a):
         expressions = 8 if a.dataset == "davis" else 3
         synthetic_dataset.make_dataset(a.root, videos=a.make_synthetic, frames=a.frames, expressions=expressions,
                                        n_words=a.words)
+        if a.dataset == "davis" and a.eval_davis:
+            synthetic_dataset.make_davis_annotations(a.root, a.eval_davis, objects=2, void=True)
     meta = os.path.join(a.root, "meta_expressions", "valid", "meta_expressions.json")
     for _ in range(600):                       # other ranks: the meta file is written last
         if os.path.exists(meta):
@@ -288,9 +290,19 @@ def _run_dataset(a):
     driver = infer_refytb if a.dataset == "refytb" else infer_davis
     model = model.to(dev).eval()
     engine = ClipInferencer(model, dev, use_graphs=a.graphs, pad_tokens_to=32, group=a.group if a.graphs else 1)   # shared across passes
+    extra = {}
+    if a.eval_davis:
+        if a.dataset != "davis":
+            raise RuntimeError("--eval-davis scores the output of --dataset davis")
+        extra = {"eval_root": a.eval_davis, "eval_task": a.eval_task}
     for _ in range(max(a.repeat, 1)):
-        stats = driver.run(model, tokenize, a.root, a.out, rank, world, dev, engine=engine)
+        stats = driver.run(model, tokenize, a.root, a.out, rank, world, dev, engine=engine, **extra)
     stats["clips_per_s"] = stats["expressions"] / stats["seconds"]
+    if "jf" in stats:
+        jf = stats["jf"]
+        print(" " * 7 + " ".join(f"{h:>9}" for h in jf["measures"]))
+        for name, row in [(f"anno_{i}", r) for i, r in enumerate(jf["per_annotator"])] + [("mean", jf["mean"])]:
+            print(f"{name:>7} " + " ".join(f"{x:9.5f}" for x in row))
     print(json.dumps({"rank": rank, "world": world, **stats}))
 
 
@@ -314,6 +326,12 @@ def parse_args(argv=None):
                     help="--graphs: consecutive clips of one geometry per launch group (each gets its single-clip result; clips of "
                          "different videos share a group when their geometry is the same; a remainder of fewer than half a group "
                          "leaves through the one-clip graph).  Default: 8 with --graphs, 1 without")
+    ap.add_argument("--eval-davis", metavar="DIR",
+                    help="--dataset davis: score the label maps against the DAVIS tree DIR (ImageSets, Annotations[_unsupervised]) on "
+                         "the device and write the J&F CSVs into each anno_<a> directory; with --make-synthetic a synthetic "
+                         "ground truth is written to DIR first")
+    ap.add_argument("--eval-task", default="unsupervised", choices=["semi-supervised", "unsupervised"],
+                    help="--eval-davis: the DAVIS task (the reference's eval_davis.py default: unsupervised)")
     ap.add_argument("--words", type=int, default=0, help="--make-synthetic: fixed number of words per expression")
     ap.add_argument("--repeat", type=int, default=1, help="run the driver this many times, report the last (warm) pass")
     ap.add_argument("--gpus", "-ng", type=int, default=None,

@@ -55,12 +55,62 @@ def save_label_map(labels: np.ndarray, path: str, palette: Sequence[int]) -> Non
         png_fast.save(path, labels.astype(np.uint8, copy=False), palette=palette)
 
 
+class _Scorer:
+    """J&F of each annotator's label maps against a DAVIS ground-truth tree, while the maps are still on the device.  A video's
+    ground truth is decoded once, on a reader thread from the moment the driver reaches the video, uploaded when its first
+    annotator arrives and dropped after its last."""
+
+    def __init__(self, eval_root: str, task: str, videos: Sequence[str], annotators: int, device):
+        from . import davis_eval
+        self.de, self.task, self.device, self.annotators = davis_eval, task, device, annotators
+        self.dataset = davis_eval.DavisDataset(eval_root, task, "val", sequences=list(videos))
+        self.results = [davis_eval.DavisJF() for _ in range(annotators)]
+        self.gt = {}                # video -> [labels on the device, objects, annotators still to come]
+        self.reader = ThreadPoolExecutor(max_workers=2)
+        self.reading = {}           # video -> future of its ground-truth label maps (PNG decoding beside the forwards)
+
+    def prefetch(self, video: str) -> None:
+        if video not in self.reading and video not in self.gt:
+            self.reading[video] = self.reader.submit(self.dataset.masks, video)
+
+    def score(self, video: str, anno: int, labels: torch.Tensor) -> None:
+        if video not in self.gt:
+            self.prefetch(video)
+            maps, _ = self.reading.pop(video).result()
+            gt = torch.from_numpy(maps).to(self.device)
+            self.gt[video] = [gt, self.de.count_objects(gt), self.annotators]
+        entry = self.gt[video]
+        if tuple(entry[0].shape) != tuple(labels.shape):
+            raise ValueError(f"{video}: ground truth {tuple(entry[0].shape)} does not match the output {tuple(labels.shape)} "
+                             "(frames, height, width)")
+        j_rows, f_rows = self.de.evaluate_sequence(entry[0], labels, self.task, num_objects=entry[1])
+        self.results[anno].add(video, j_rows, f_rows)
+        entry[2] -= 1
+        if entry[2] == 0:
+            del self.gt[video]
+
+    def finish(self, out_dir: str) -> Dict:
+        self.reader.shutdown()
+        rows = [r.global_row() for r in self.results]
+        for anno, r in enumerate(self.results):
+            os.makedirs(os.path.join(out_dir, f"anno_{anno}"), exist_ok=True)
+            self.de.write_csvs(r, os.path.join(out_dir, f"anno_{anno}"), "val")
+        return {"task": self.task, "measures": list(self.de.G_MEASURES), "per_annotator": rows,
+                "mean": self.de.mean_rows(rows),
+                "per_sequence": [[list(x) for x in r.per_sequence()] for r in self.results]}
+
+
 @torch.no_grad()
 def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world: int = 1, device="cuda",
         split: str = "valid", size: int = 360, max_size: Optional[int] = 640, use_graphs: bool = False,
         decode_workers: int = 8, writer_workers: int = 16, palette: Optional[Sequence[int]] = None,
         videos: Optional[Sequence[str]] = None, annotators: int = 4,
-        engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1) -> Dict:
+        engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1,
+        eval_root: Optional[str] = None, eval_task: str = "unsupervised") -> Dict:
+    """eval_root: a DAVIS tree (ImageSets/2017/val.txt, Annotations[_unsupervised]/480p).  When given, every annotator's label
+    maps are scored against it on the device, as the reference's eval_davis.py scores the PNGs afterwards (davis_eval, K27):
+    stats["jf"] holds the global row per annotator and their mean, and the two CSVs are written into each anno_<a> directory.
+    The PNGs and everything else the driver does are the same with and without it."""
     img_folder, data = load_meta(root, split)
     if palette is None:
         ref_png = os.path.join(root, split, "Annotations", "blackswan", "00000.png")
@@ -70,6 +120,11 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         else:
             palette = davis_palette()
     todo = split_videos(sorted(data.keys()) if videos is None else list(videos), rank, world)
+    scorer = None
+    if eval_root is not None:
+        if world != 1:
+            raise ValueError("eval_root: the tables cover every video of the set, so scoring runs in one process (world = 1)")
+        scorer = _Scorer(eval_root, eval_task, todo, annotators, device)
     engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group)
     cache = clip_io.VideoClipCache(clip_io.FramePreprocessor(device, size, max_size), workers=decode_workers)
     stats = {"videos": 0, "expressions": 0, "frames": 0, "seconds_input": 0.0, "seconds_model": 0.0}
@@ -93,7 +148,13 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
             job = waiting.pop(0)
             t2 = time.perf_counter()
             per_obj = torch.stack([torch.cat(chunks, 0) for chunks in job["got"]])
-            labels = hot_ops.upsample_merge_labels(per_obj, job["orig"]).cpu().numpy()   # [T,H0,W0]
+            labels = hot_ops.upsample_merge_labels(per_obj, job["orig"])                 # [T,H0,W0], on the device
+            if scorer is not None:
+                t3 = time.perf_counter()
+                scorer.score(job["video"], job["anno"], labels)
+                t2 += time.perf_counter() - t3
+                stats["seconds_eval"] = stats.get("seconds_eval", 0.0) + time.perf_counter() - t3
+            labels = labels.cpu().numpy()
             stats["seconds_model"] += time.perf_counter() - t2    # waits for this annotator's forwards
             os.makedirs(job["save_dir"], exist_ok=True)
             for f in range(labels.shape[0]):
@@ -105,6 +166,8 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         for vi, video in enumerate(todo):
             frames = data[video]["frames"]
             exps = data[video]["expressions"]
+            if scorer is not None:
+                scorer.prefetch(video)
             if vi + 1 < len(todo):      # decode the next video's first clip while this one is on the GPU
                 nxt = todo[vi + 1]
                 cache.prefetch(clip_io.frame_paths(img_folder, nxt, data[nxt]["frames"][:CLIP_LEN]))
@@ -114,7 +177,7 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
             for anno in range(annotators):
                 ids = [tokenize(exps[exp_ids[obj * annotators + anno]]["exp"]).to(device) for obj in range(num_obj)]
                 job = {"got": [[None] * len(starts) for _ in range(num_obj)], "left": num_obj * len(starts), "orig": None,
-                       "save_dir": os.path.join(out_dir, f"anno_{anno}", video)}
+                       "save_dir": os.path.join(out_dir, f"anno_{anno}", video), "video": video, "anno": anno}
                 waiting.append(job)
                 for ci, c0 in enumerate(starts):
                     t1 = time.perf_counter()
@@ -143,4 +206,6 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
     cache.close()
     stats.update(seconds=time.perf_counter() - t0, cache_hits=cache.hits, cache_misses=cache.misses)
     stats.update({k: v for k, v in getattr(engine, "stats", {}).items()})       # group replays, part-filled ones, remainders
+    if scorer is not None:
+        stats["jf"] = scorer.finish(out_dir)
     return stats

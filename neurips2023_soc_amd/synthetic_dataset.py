@@ -107,3 +107,61 @@ def make_dataset(root: str, videos: int = 2, frames: int = 8, height: int = 720,
     with open(os.path.join(mdir, "meta_expressions.json"), "w") as f:
         json.dump(meta, f)
     return root
+
+
+def blob_label_maps(seed: int, frames: int, height: int, width: int, objects: int, void: bool = False,
+                    wobble: float = 0.0, labels: Sequence[int] = ()) -> np.ndarray:
+    """uint8 [frames, height, width] label maps of `objects` drifting ellipses (later ones on top), labelled 1..objects or
+    by `labels`.  Ellipse k depends on (seed, k) only; wobble > 0 perturbs centre and radii per frame, so the maps of one seed
+    with and without wobble are a ground truth and a plausible prediction of it.  void=True paints discs of label 255 that
+    straddle the objects' outlines (DAVIS marks uncertain borders that way)."""
+    noise = np.random.default_rng(seed + 7919)
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    dims = np.array([height, width], dtype=np.float64)
+    draws = [np.random.default_rng([seed, k]).uniform(0, 1, 7) for k in range(objects)]      # object k: (seed, k) only
+    centre = np.array([0.2 + 0.6 * d[0:2] for d in draws]).reshape(objects, 2) * dims
+    radii = np.array([0.08 + 0.22 * d[2:4] for d in draws]).reshape(objects, 2) * dims + 1.0
+    speed = np.array([0.06 * d[4:6] - 0.03 for d in draws]).reshape(objects, 2) * dims
+    phase = np.array([2 * np.pi * d[6] for d in draws])
+    out = np.zeros((frames, height, width), dtype=np.uint8)
+    for t in range(frames):
+        for k in range(objects):
+            c = centre[k] + speed[k] * t + wobble * noise.normal(0, 1, 2) * dims
+            r = radii[k] * (1 + wobble * noise.normal(0, 1, 2)).clip(0.2)
+            out[t][((yy - c[0]) / r[0]) ** 2 + ((xx - c[1]) / r[1]) ** 2 <= 1] = labels[k] if len(labels) else k + 1
+        if void:
+            for k in range(objects):
+                c = centre[k] + speed[k] * t
+                a = phase[k] + 0.7 * t
+                p = c + radii[k] * np.array([np.sin(a), np.cos(a)])
+                out[t][(yy - p[0]) ** 2 + (xx - p[1]) ** 2 <= (0.05 * min(height, width) + 1) ** 2] = 255
+    return out
+
+
+def make_davis_annotations(root: str, davis_root: str, objects: int = 2, void: bool = False, seed: int = 0,
+                           split: str = "valid", subset: str = "val") -> str:
+    """A DAVIS-layout ground-truth tree for the videos of a make_dataset tree under `root`, so that the DAVIS driver's
+    output can be scored offline: <davis_root>/ImageSets/2017/<subset>.txt and palette PNGs of seeded blob label maps
+    (blob_label_maps) under Annotations/480p and Annotations_unsupervised/480p, <video>/<%05d>.png in frame order -- the
+    names the driver gives its output.  Stand-in data: the scores say nothing about a model."""
+    from PIL import Image
+    from .infer_davis import davis_palette
+    with open(os.path.join(root, "meta_expressions", split, "meta_expressions.json")) as f:
+        videos = json.load(f)["videos"]
+    palette = davis_palette()
+    os.makedirs(os.path.join(davis_root, "ImageSets", "2017"), exist_ok=True)
+    with open(os.path.join(davis_root, "ImageSets", "2017", f"{subset}.txt"), "w") as f:
+        f.write("".join(name + "\n" for name in sorted(videos)))
+    for v, name in enumerate(sorted(videos)):
+        names = videos[name]["frames"]
+        with Image.open(os.path.join(root, split, "JPEGImages", name, names[0] + ".jpg")) as img:
+            width, height = img.size
+        maps = blob_label_maps(seed * 1000 + v, len(names), height, width, objects, void=void)
+        for folder in ("Annotations", "Annotations_unsupervised"):
+            d = os.path.join(davis_root, folder, "480p", name)
+            os.makedirs(d, exist_ok=True)
+            for t in range(len(names)):
+                png = Image.fromarray(maps[t])
+                png.putpalette(palette)
+                png.save(os.path.join(d, f"{t:05d}.png"))
+    return davis_root
