@@ -481,8 +481,8 @@ int soc_groupnorm_nchw_f32(const float* x, const float* bias, const float* gamma
  * K18 -- lateral connection of the FPN spatial decoder (reference models/segmentation.py:62-72:
  * `cur_fpn + F.interpolate(x, size=cur_fpn.shape[-2:], mode="nearest")`):
  *   y[n,c,h,w] = lateral[n,c,h,w] + bias[c] + prev[n, c, min(floor(h * Hp / H), Hp-1), min(floor(w * Wp / W), Wp-1)]
- * (the float index rule of F.interpolate(mode="nearest")).  lateral, y [N,C,H,W]; prev [N,C,Hp,Wp]; bias [C] or NULL
- * (the adapter convolution's bias when that was run without one).
+ * (the float index rule of F.interpolate(mode="nearest")).  lateral, y [N,C,H,W] (y may alias lateral); prev [N,C,Hp,Wp];
+ * bias [C] or NULL (the adapter convolution's bias when that was run without one).
  */
 int soc_upsample_add_nchw_f32(const float* lateral, const float* bias, const float* prev, float* y, int N, int C, int H,
                               int W, int Hp, int Wp, void* stream);

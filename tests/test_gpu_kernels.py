@@ -588,7 +588,8 @@ def test_conv3x3_tokens_vs_torch(ops, N, H, W, Cin, Cout, nchw, relu):
     assert got.shape == want.shape
     assert maxdiff(got, want.float()) < 3e-5
     # frames read in place out of a wider buffer (a level slice of the encoder memory)
-    wide = torch.zeros(N, H * W + 13, Cin, device="cuda")
+    # whose slack is NaN: a halo row read from the neighbouring tokens and multiplied by a zero mask would show
+    wide = torch.full((N, H * W + 13, Cin), float("nan"), device="cuda")
     wide[:, 5:5 + H * W] = tok
     got2 = ops.conv3x3_tokens(wide[:, 5:5 + H * W], (H, W), taps, dev(b), out_nchw=nchw, relu=relu)
     if not nchw:
