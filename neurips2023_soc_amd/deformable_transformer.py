@@ -10,6 +10,7 @@ from torch import nn
 from . import fused, hot_ops
 from .fused import linear_relu
 from .attention import HipMultiheadAttention
+from .derived_cache import hold
 from .ms_deform_attn import MSDeformAttn
 
 
@@ -177,7 +178,7 @@ class DeformableTransformer(nn.Module):
         if key not in cache:
             ss = torch.as_tensor(shapes, dtype=torch.long, device=device)
             cache[key] = (ss, torch.cat((ss.new_zeros(1), ss.prod(1).cumsum(0)[:-1])))
-        return cache[key]
+        return hold(cache[key])
 
     @staticmethod
     def get_valid_ratio(mask):
@@ -190,7 +191,10 @@ class DeformableTransformer(nn.Module):
         """Everything encode() derives from the geometry alone when no frame is padded (~95 tiny
         launches, 0.45 ms at the BASELINE config): the all-False mask, valid ratios = 1, the K2 pad flag
         = 0, the encoder reference points and pos + level_embed.  Cached per (geometry, level_embed
-        version), like the reference caches compute_mask per geometry (video_swin_transformer.py:316)."""
+        version), like the reference caches compute_mask per geometry (video_swin_transformer.py:316).
+        The cache is bounded: the 18th distinct key drops the 17 entries before it.  That frees only what nobody holds -- a graph
+        runner that was handed an entry during its warm-up and capture keeps it (derived_cache.keep_alive) for as long as the
+        runner lives, whatever happens to the entry here."""
         cache = self.__dict__.setdefault("_unpadded_cache", {})
         key = (shapes, n, str(device), self.level_embed.data_ptr(), self.level_embed._version,
                tuple(p.data_ptr() for p in pos_embeds))
@@ -207,7 +211,7 @@ class DeformableTransformer(nn.Module):
                 "pos": torch.cat([pe.flatten(2).transpose(1, 2) + self.level_embed[lvl].view(1, 1, -1)
                                   for lvl, pe in enumerate(pos_embeds)], 1),
             }
-        return cache[key]
+        return hold(cache[key])
 
     def encode(self, srcs, masks, pos_embeds, token_major=False, unpadded=False, maps=True):
         """Flatten the levels and run the deformable encoder.  Returns (memory maps of the 3 finest

@@ -2,7 +2,55 @@
 weak 12), which re-exports DerivedCache."""
 from __future__ import annotations
 
+import threading
+
 from torch import Tensor
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Lifetime contract of every host-side cache of device tensors (the DerivedCache instances, hot_ops._ws_cache, the transformer's
+# _unpadded_cache / _shape_cache, Joiner._pos_cache, the FPN's _tap_cache).  A captured hipGraph has the ADDRESSES of whatever
+# these caches handed out during its warm-up and capture baked in, so those values must stay allocated for as long as the graph
+# can be replayed -- whatever the cache does with its entry afterwards (bounded eviction, rebuild after a weight update).  A
+# graph runner therefore opens a keep-alive scope around its warm-up and capture; each cache passes every value it hands out
+# through hold(), which appends it to the open scopes.  The runner keeps the list: what it was handed lives exactly as long as
+# the runner object, and evicting the runner releases it.  Outside a scope hold() is one attribute test; nothing of this sits on
+# the replay path, which does not enter Python's forward at all.
+_tls = threading.local()
+
+
+class keep_alive:
+    """`with keep_alive(holder):` -- every cached value handed out on this thread inside the block is appended (once) to the
+    list `holder`.  Scopes nest: a value goes to every open scope."""
+
+    def __init__(self, holder: list):
+        self.holder = holder
+        self._ids = {id(v) for v in holder}     # ids stay unique while the holder keeps the values alive
+
+    def add(self, value):
+        if id(value) not in self._ids:
+            self._ids.add(id(value))
+            self.holder.append(value)
+
+    def __enter__(self):
+        scopes = getattr(_tls, "scopes", None)
+        if scopes is None:
+            scopes = _tls.scopes = []
+        scopes.append(self)
+        return self.holder
+
+    def __exit__(self, *exc):
+        _tls.scopes.pop()               # scopes close in the reverse order of opening
+        return False
+
+
+def hold(value):
+    """Called by a cache on every value it hands out (hit or miss); returns the value."""
+    scopes = getattr(_tls, "scopes", None)
+    if scopes:
+        for scope in scopes:
+            scope.add(value)
+    return value
 
 
 class DerivedCache:
@@ -13,7 +61,9 @@ class DerivedCache:
     so that views created per call (`in_proj_weight[:E]`) hit, and a contiguous copy made on the way never enters the key.  An
     entry holds only WEAK references to the tensors' owners (the view's base, i.e. the nn.Parameter): the model can be freed,
     and when it is, the entry -- and the device memory of the image -- goes with it.  Nothing is ever bulk-cleared: a captured
-    hipGraph that has a packed image's address baked in keeps its model alive, and with the model the entry.
+    hipGraph that has a packed image's address baked in keeps its model alive, and with the model the entry.  An entry that is
+    REPLACED (rebuild after a weight update) does not free an image a live graph uses either: the graph's runner holds every
+    value it was handed (keep_alive / hold above).
 
     Update weights in place under no_grad (`p.copy_(w)`, `load_state_dict`): that bumps `_version` and the image is rebuilt.
     A write through `p.data` (`p.data.copy_(w)`) does NOT bump the version and cannot be seen here -- do not load weights that
@@ -37,13 +87,13 @@ class DerivedCache:
         if hit is not None and hit[0] == version:
             owners = [r() for r in hit[2]]
             if all(o is not None and o.data_ptr() == ptr for o, ptr in zip(owners, hit[3])):
-                return hit[1]
+                return hold(hit[1])
             self._d.pop(key, None)      # an owner died or was re-pointed (`p.data = new`): the address may belong to someone else
         value = build()
         owners = [t._base if t._base is not None else t for t in ts]
         refs = tuple(weakref.ref(o, lambda _r, k=key: self._d.pop(k, None)) for o in owners)
         self._d[key] = (version, value, refs, tuple(o.data_ptr() for o in owners))
-        return value
+        return hold(value)
 
     def __len__(self):
         return len(self._d)

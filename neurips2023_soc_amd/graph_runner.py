@@ -15,6 +15,7 @@ import torch
 from . import clip_parallel as CP
 from . import hot_ops
 from . import postprocessing as P
+from .derived_cache import keep_alive
 from .nested_tensor import NestedTensor
 
 
@@ -48,9 +49,25 @@ def switches_set() -> Dict[str, str]:
 CAPTURE_MODE = "thread_local"
 
 
+def _holds_what_it_captures(init):
+    """A runner's __init__ (warm-up forwards + captures) inside a keep-alive scope: whatever the host-side caches hand out there
+    -- geometry constants, packed weight images, workspaces; the captured graphs have their addresses baked in -- is appended
+    to `self._held` and so stays allocated for exactly as long as the runner object lives (derived_cache.keep_alive), whatever
+    the caches do with their entries later.  Evicting the runner (ClipInferencer) releases it.  Nothing of this runs on replay."""
+    import functools
+
+    @functools.wraps(init)
+    def wrapped(self, *args, **kwargs):
+        self._held = []
+        with keep_alive(self._held):
+            return init(self, *args, **kwargs)
+    return wrapped
+
+
 class ClipGraph:
     CLIPS = 1              # clips per replay
 
+    @_holds_what_it_captures
     def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
         self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
         self.device = torch.device(device)
@@ -129,6 +146,7 @@ class PipelinedClipGraph:
     DEPTH = 2
     CLIPS = 1              # clips per replay (PairPipelinedClipGraph: 2)
 
+    @_holds_what_it_captures
     def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
         self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
         dev = self.device = torch.device(device)
@@ -313,6 +331,7 @@ class TwoStreamClipGraph(PipelinedClipGraph):
     call earlier, flush() drains.
     """
 
+    @_holds_what_it_captures
     def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
         self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
         dev = self.device = torch.device(device)
@@ -499,6 +518,7 @@ class PairPipelinedClipGraph(PipelinedClipGraph):
 
     CLIPS = 2
 
+    @_holds_what_it_captures
     def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
         self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
         dev = self.device = torch.device(device)

@@ -454,7 +454,7 @@ def mha_core(q: Tensor, k: Tensor, v: Tensor, n_heads: int,
         if ws is None or ws.numel() < need:
             ws = torch.empty(need, dtype=torch.uint8, device=q.device)
             _ws_cache[key] = ws
-        ws_ptr = ws.data_ptr()
+        ws_ptr = hold(ws).data_ptr()     # a larger need replaces the entry: a live graph's runner keeps the one it captured
     with _timed("xattn", (2 * q.numel() + k.numel() + v.numel()) * 4):
         code = lib.soc_xattn_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), kpm_ptr, am_ptr, am_heads, out.data_ptr(),
                                  Lq, Lk, B, n_heads, hd, int(bool(batch_first)), ws_ptr, need, _stream())
@@ -869,7 +869,7 @@ def ws_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, ln: Opti
 
 # The arithmetic mode of a forward and the routing rules that hang on it live in matmul_mode.py, the cache of packed weight images
 # in derived_cache.py; both are re-exported here (callers and tests use hot_ops.<name>).
-from .derived_cache import DerivedCache  # noqa: E402,F401
+from .derived_cache import DerivedCache, hold, keep_alive  # noqa: E402,F401
 from .matmul_mode import (DEFAULT_MATMUL_MODE, _SPLIT_OFF, _mode_tls, k1_split_enabled, k13_split_enabled,  # noqa: E402,F401
                           matmul_mode, split_enabled, split_wins, use_matmul_mode)
 

@@ -24,11 +24,40 @@ from .graph_runner import ClipGraph, PipelinedClipGraph, pipeline_class
 from .nested_tensor import NestedTensor
 
 
+class _WeightsEpoch:
+    """load_state_dict post-hook on every module of a model: counts the loads (of the model or of any part of it).  A class, not
+    a closure, so that a model carrying it can still be pickled and deep-copied."""
+
+    def __init__(self):
+        self.n = 0
+
+    def __call__(self, module, incompatible_keys):
+        self.n += 1
+
+
+def weights_epoch(model) -> _WeightsEpoch:
+    """The model's load counter (installed on first use).  Captured graphs have the weights' packed images and, for biases and
+    norm parameters, the parameters' own addresses baked in: after a load a graph captured before it would compute with a mix
+    of old and new weights, so ClipInferencer compares `.n` (one integer, no walk over the parameters) on every call and drops
+    its graphs when it moved."""
+    epoch = model.__dict__.get("_soc_weights_epoch")
+    if epoch is None:
+        epoch = model.__dict__["_soc_weights_epoch"] = _WeightsEpoch()
+        for m in model.modules():
+            m.register_load_state_dict_post_hook(epoch)
+    return epoch
+
+
 class ClipInferencer:
     """model + (optionally) one hipGraph per (T, H, W, L) geometry.  `__call__` returns the reference
     driver's per-clip products: selected query index, its mask logits, and the thresholded full-size
     masks.  use_graphs=True pays off on streams of one geometry (bench, DAVIS 36-frame clips); whole-video
-    clips with free-form expressions (Ref-YouTube-VOS: T and L change per call) run eagerly."""
+    clips with free-form expressions (Ref-YouTube-VOS: T and L change per call) run eagerly.
+
+    Weights: a `load_state_dict` on the model (or a part of it) and a move of the model to another device and back are noticed
+    on the next call, which drops every captured graph and captures afresh under the new weights (weights_epoch; with clips
+    still staged or in flight the call raises instead: drain() first).  An in-place edit of single parameters
+    (`p.copy_(w)` under no_grad) is seen by the eager forward but NOT by a captured graph: call reset() after it."""
 
     PAD_ID = 1            # RoBERTa <pad>
 
@@ -53,7 +82,38 @@ class ClipInferencer:
         self._pipes: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}
         self._singles: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}     # one-clip pipelines for the remainders of groups
         self._active = None          # (key, pipe, tag of the clip in flight)
-        self.stats = {"group_replays": 0, "part_filled_replays": 0, "stale_slots": 0, "remainder_singles": 0}
+        self.stats = {"group_replays": 0, "part_filled_replays": 0, "stale_slots": 0, "remainder_singles": 0,
+                      "weight_reloads_seen": 0}
+        watched = use_graphs and isinstance(model, torch.nn.Module)      # (anything else has no load_state_dict to watch)
+        self._epoch = weights_epoch(model) if watched else None
+        self._probe = next(model.parameters(), None) if watched else None        # re-pointed by model.cpu() / .cuda() / .to()
+        self._captured_under = self._weights_state()
+
+    def _weights_state(self):
+        if self._epoch is None:
+            return None
+        return (self._epoch.n, None if self._probe is None else self._probe.data_ptr())
+
+    def _check_weights(self):
+        """Drop every graph that was captured under other weights than the model has now.  Two integers per call; not on the
+        replay path of a runner (graph_runner), which callers that own their runner drive directly."""
+        if self._epoch is not None and self._weights_state() != self._captured_under:
+            if self._active is not None or self._filling:
+                raise RuntimeError("the model's weights changed while clips are staged or in flight: drain() before loading weights")
+            self.stats["weight_reloads_seen"] += 1
+            self.reset()
+
+    def reset(self):
+        """Drop every captured graph (and with it the packed weight images and geometry constants it held); the next call of a
+        geometry captures again.  Needed by hand after in-place edits of single parameters (`p.copy_`) only."""
+        if self._active is not None or self._filling:
+            raise RuntimeError("clips are staged or in flight: drain() first")
+        if self._graphs or self._pipes or self._singles:
+            torch.cuda.synchronize(self.device)              # never drop a graph that may still be replaying
+        self._graphs.clear()
+        self._pipes.clear()
+        self._singles.clear()
+        self._captured_under = self._weights_state()
 
     def graph_for(self, T: int, H: int, W: int, L: int) -> ClipGraph:
         key = (T, H, W, L)
@@ -120,6 +180,7 @@ class ClipInferencer:
         the caller as soon as submit returns (it has been copied into the graph's static input)."""
         if not self.use_graphs:
             raise RuntimeError("submit() streams through hipGraphs; construct with use_graphs=True")
+        self._check_weights()
         T, _, H, W = clip.shape
         ids, attn = self._pad_tokens(token_ids)
         key = (T, H, W, ids.shape[-1])
@@ -191,6 +252,7 @@ class ClipInferencer:
         """-> (reference output dict, packed record or None)"""
         T, _, H, W = clip.shape
         if self.use_graphs:
+            self._check_weights()
             ids, attn = token_ids.view(1, -1), None
             L = ids.shape[-1]
             if self.pad_tokens_to is not None and L < self.pad_tokens_to:

@@ -16,6 +16,7 @@ import torch
 from torch import Tensor, nn
 
 from . import hot_ops
+from .derived_cache import hold
 
 
 class FPNSpatialDecoder(nn.Module):
@@ -50,7 +51,7 @@ class FPNSpatialDecoder(nn.Module):
         if ent is None or ent[0] != (w.data_ptr(), w._version, str(w.device)):
             cache[key] = ((w.data_ptr(), w._version, str(w.device)),
                           w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous())
-        return cache[key][1]
+        return hold(cache[key][1])        # a rebuild replaces the entry: a live graph's runner keeps the image it captured
 
     def tokens_supported(self, memory: Tensor) -> bool:
         convs = [self.lay1, self.lay2, self.lay3, self.lay4] + ([self.lay5] if self.add_extra_layer else []) + [self.out_lay]

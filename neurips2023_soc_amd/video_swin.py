@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import fused, hot_ops
+from .derived_cache import hold
 from .nested_tensor import NestedTensor
 from .position_encoding import PositionEmbeddingSine2D
 
@@ -385,7 +386,7 @@ class Joiner(nn.Sequential):
         key = (tuple(x.mask.shape), str(x.mask.device))
         if key not in cache:
             cache[key] = self[1](NestedTensor(x.tensors, torch.zeros_like(x.mask))).to(x.tensors.dtype)
-        return cache[key]
+        return hold(cache[key])
 
 
 def build_video_swin_backbone(args) -> Joiner:
