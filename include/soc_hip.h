@@ -274,8 +274,8 @@ int soc_patch_merge_layernorm_f32(const float* x, const float* gamma, const floa
  *   soc_mlp_split_packed_bytes / soc_mlp_split_pack_f32: split and lay out both weights ONCE (opaque image `packed`);
  *   re-pack after the weights change.  soc_mlp_split_workspace_bytes: scratch for the partial sums (0 when none are needed).
  *   soc_mlp_split_plan: the (workgroup rows, hidden ranges) cut chosen for M rows taken as ONE launch.
- *   soc_mlp_split_variant_f32: one launch with an explicit cut (workspace: nfs * M * C floats when nfs > 1); `variant` 0 is
- *   the shipped kernel, other values exist in diagnostic builds only (SOC_K23_VARIANTS) and return SOC_EUNSUPPORTED otherwise.
+ *   soc_mlp_split_variant_f32: one launch with an explicit cut (workspace: nfs * M * C floats when nfs > 1); `variant` must be 0
+ *   (the one kernel form of the width); any other value is unsupported and returns SOC_EUNSUPPORTED.
  */
 size_t soc_mlp_split_packed_bytes(int C, int F);
 int soc_mlp_split_pack_f32(const float* w1, const float* w2, void* packed, int C, int F, void* stream);

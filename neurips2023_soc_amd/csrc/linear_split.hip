@@ -32,13 +32,12 @@
 //   * an XCD works through a contiguous range of tiles (column tiles of one row panel next to each other), so a row
 //     panel of x is fetched once per XCD L2.
 #include "soc_common.h"
+#include "split_math.h"
 #include <math.h>
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace soc_split;
 
 constexpr int BK = 32;        // k per step
 constexpr int ROWB = 64;      // bytes per LDS / packed row (32 bf16)
@@ -78,48 +77,11 @@ extern "C" void soc_debug_set_buffer_k20(void* ptr) { g_dbg20 = (unsigned long l
 #define STAMP20(i) do {} while (0)
 #endif
 
-// exact (erf) GELU with erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, ~1 ulp of the 1 + erf it is added to),
-// branch-free (libm's erff is piecewise: 16 divergent branches per tile row group) -- the form K13 uses
-// The constants live in vector registers (GeluConsts, filled through an opaque v_mov): the compiler would otherwise feed
-// them to v_pk_fma_f32 from SGPR pairs, the operand form that is unsafe beside LDS-DMA + MFMA waves (see the kernel).
-struct GeluConsts { float rs2, a0, one, c5, c4, c3, c2, c1, nlog2e, half; };
-__device__ __forceinline__ float in_vgpr(float c) {
-    float r;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(c));
-    return r;
-}
-__device__ __forceinline__ GeluConsts gelu_consts() {
-    return {in_vgpr(0.70710678118654752f), in_vgpr(0.3275911f), in_vgpr(1.0f), in_vgpr(1.061405429f), in_vgpr(-1.453152027f),
-            in_vgpr(1.421413741f), in_vgpr(-0.284496736f), in_vgpr(0.254829592f), in_vgpr(-1.4426950408889634f),
-            in_vgpr(0.5f)};
-}
-__device__ __forceinline__ float gelu_erf(float x, const GeluConsts& k) {
-    const float z = fabsf(x) * k.rs2;
-    const float t = __builtin_amdgcn_rcpf(fmaf(k.a0, z, k.one));
-    float p = fmaf(k.c5, t, k.c4);
-    p = fmaf(p, t, k.c3);
-    p = fmaf(p, t, k.c2);
-    p = fmaf(p, t, k.c1);
-    const float e = __builtin_amdgcn_exp2f(z * z * k.nlog2e);
-    const float erf_abs = fmaf(-p * t, e, k.one);         // erf(|x| / sqrt 2)
-    const float half = k.half * x;
-    return fmaf(half, copysignf(erf_abs, x), half);        // 0.5 x (1 + erf(x / sqrt 2))
-}
-
-// f32 x 8 -> three bf16 x 8 with a0 + a1 + a2 == a exactly (round-to-nearest at every level)
+// the shared split (split_math.h) as the 16-B pieces the LDS image and the packed weights are written in
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4& p0, u32x4& p1, u32x4& p2) {
     bf16x8 h0, h1, h2;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a0 = (__bf16)v[i];
-        const float r1 = v[i] - (float)a0;
-        const __bf16 a1 = (__bf16)r1;
-        const float r2 = r1 - (float)a1;
-        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
-    }
-    p0 = __builtin_bit_cast(u32x4, h0);
-    p1 = __builtin_bit_cast(u32x4, h1);
-    p2 = __builtin_bit_cast(u32x4, h2);
+    soc_split::split8(v, h0, h1, h2);
+    p0 = __builtin_bit_cast(u32x4, h0); p1 = __builtin_bit_cast(u32x4, h1); p2 = __builtin_bit_cast(u32x4, h2);
 }
 
 constexpr int SCRW = 36;                       // floats per row of a wave's 32 x 32 epilogue scratch tile
@@ -137,7 +99,6 @@ __global__ __launch_bounds__(THREADS, 2) void linear_split_kernel(const SplitPar
     constexpr int BUF_BYTES = 3 * (BM + BN) * ROWB;
     static_assert(8 * SCR_BYTES <= BUF_BYTES, "epilogue scratch lives in a tile buffer");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // [buf 0][buf 1]
-#ifndef SOC_K20_SHARE_CU
     // The kernel owns its CUs.  Measured on MI355X (tools/experiments/pk_mfma_probe.hip): while a wave that issues
     // LDS-DMA loads next to bf16 MFMAs is resident, v_pk_*_f32 instructions with an SGPR source that OTHER waves of the
     // same SIMD execute return wrong low halves in lanes 48..63 -- other kernels included (the dynamic mask head beside
@@ -145,12 +106,11 @@ __global__ __launch_bounds__(THREADS, 2) void linear_split_kernel(const SplitPar
     // waves per SIMD of one workgroup fill the 512-entry register file, so nothing else can be resident beside them;
     // this kernel's own VALU code keeps packed f32 arithmetic away from SGPR operands (checked in the build's ISA test).
     asm volatile("v_mov_b32 v255, 0" ::: "v255");
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const GeluConsts gk = gelu_consts();
+    const GeluK gk = gelu_k();
 #ifdef SOC_K20_STAMPS
     unsigned long long phase_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long last_ = __builtin_amdgcn_s_memtime();
@@ -493,8 +453,6 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     }
 }
 
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
-
 template <int MT, int NT, int WM, int WN>
 int launch_cfg(const SplitParams& p0, hipStream_t st) {
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
@@ -503,23 +461,10 @@ int launch_cfg(const SplitParams& p0, hipStream_t st) {
     p.tiles_n = (p.N + BN - 1) / BN;
     if (tiles_m * p.tiles_n >= (1L << 31)) return SOC_EUNSUPPORTED;
     p.total_tiles = (int)(tiles_m * p.tiles_n);
-#ifndef SOC_K20_DBG_PAD
-#define SOC_K20_DBG_PAD 0
-#endif
-    const size_t lds = 2 * 3 * (BM + BN) * ROWB + SOC_K20_DBG_PAD;
+    const size_t lds = 2 * 3 * (BM + BN) * ROWB;
     if (lds > 160 * 1024) return SOC_EUNSUPPORTED;
-    const void* fn = reinterpret_cast<const void*>(linear_split_kernel<MT, NT, WM, WN>);
-    static bool attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SOC_ELAUNCH;
-        attr_set[dev] = true;
-    }
-    long blocks = num_cus(st);
-#ifdef SOC_K20_DBG_BLOCKS_PER_CU
-    blocks *= SOC_K20_DBG_BLOCKS_PER_CU;
-#endif
+    if (soc_allow_lds<linear_split_kernel<MT, NT, WM, WN>>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
+    long blocks = soc_num_cus(st);       // CUs the launch stream may use
     if (blocks > p.total_tiles) blocks = p.total_tiles;
     hipLaunchKernelGGL((linear_split_kernel<MT, NT, WM, WN>), dim3((unsigned)blocks), dim3(THREADS), lds, st, p);
     return soc_check_launch();

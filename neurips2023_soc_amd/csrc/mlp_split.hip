@@ -21,19 +21,19 @@
 //     handed over with a COUNTED vmcnt wait: only the piece needed next must have landed;
 //   * the LDS-DMA is issued from inline assembly (see dma below): with a compiler-visible LDS-DMA in flight every LDS wait of
 //     the loop degrades to lgkmcnt(0) and fragment reads cannot run ahead of the MFMAs;
-//   * weight fragments are read PF groups ahead of the MFMAs that consume them (sched_group_barrier pins the order).
+//   * weight fragments are read one group ahead of the MFMAs that consume them (sched_group_barrier pins the order).
 // Every row is taken: a workgroup owns a balanced contiguous share of the row tiles and deals the tiles of a part-filled pass
 // round-robin over its waves (one per SIMD first); for few rows the hidden dimension is split over `nfs` workgroup columns
 // that write partial sums, which a reduce kernel adds in a fixed order (deterministic) together with b2 / residual / LN2.
 // C <= 256: eight 256-register waves (two per SIMD); C = 384 / 512 (Swin-B stage 2): four 512-register waves, blocks travel as
 // half-block pieces.
-// Measured null and kept as diagnostic variants only (SOC_K23_VARIANTS): waves 4..7 one piece behind waves 0..3, the
-// activation at raised wave priority, deeper fragment prefetch, four-wave forms for C <= 256 (tools/experiments/README.md).
+// Measured null and not kept: waves 4..7 one piece behind waves 0..3, the activation at raised wave priority, the LDS-DMA
+// spread between the MFMA groups, deeper fragment prefetch, other ring shapes (numbers: tools/experiments/README.md; the code
+// was last in commit fc20909).
 // Co-residence rule: the whole register file is claimed, waves retire behind a barrier, packed f32 code
 // has VGPR operands only (tests/test_isa_rules.py).
 #include "soc_common.h"
 #include "split_math.h"
-#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -41,43 +41,48 @@ namespace {
 using namespace soc_split;
 constexpr int MAX_THREADS = 512;       // the image pads a block to whole DMA rounds of 512 threads (256-thread forms take two)
 
+// The form of a width.  Waves per workgroup and row tiles per wave: 256-register waves (NW = 8, two per SIMD) hold the x
+// fragments (3 C / 8 registers per tile) and the output accumulators (C / 4 per tile) of RT tiles up to C = 256; C = 384 / 512
+// need the 512 registers of a one-wave-per-SIMD workgroup (wider rows, so that a weight fragment read from LDS feeds as many
+// MFMAs).  The ring: a block of C <= 256 is one piece, three or four slots; the 72-KB blocks of C = 384 travel as halves
+// (36 KB) through four slots -- two whole-block slots would leave one block in flight, too little to cover the L2 latency.
+constexpr int form_nw(int C) { return C > 256 ? 4 : 8; }
+constexpr int form_rt(int C) { return C <= 96 ? 2 : 1; }
+constexpr int form_sb(int C) { return C > 256 ? 2 : 1; }
+constexpr int tiles_per_pass(int C) { return form_nw(C) * form_rt(C); }
+
 template <int C>
 struct Geo {
     static constexpr int KS = C / 32;                                   // k-steps of the first product
     static constexpr int OT = C / 16;                                   // output tiles of the second product
     static constexpr int BLK_U4 = OT * 3 * 64;                          // 16-B pieces of a weight block (W1: 2 KS groups, W2: OT)
     static constexpr int BLKP_U4 = (BLK_U4 + MAX_THREADS - 1) / MAX_THREADS * MAX_THREADS;     // a block in the image / a ring slot
+    static constexpr int NW = form_nw(C), RT = form_rt(C);              // waves per workgroup, row tiles per wave
+    static constexpr int SB = form_sb(C);                               // ring pieces per block
+    static constexpr int SLOT_U4 = BLKP_U4 / SB;                        // a ring piece = a ring slot
+    static constexpr int RING_ROOM = 160 * 1024 - 8 * C - 4096;         // beside gamma / beta and a 1024-wide b1 range
+    static constexpr int NSLOT = RING_ROOM / (SLOT_U4 * 16) >= 4 ? 4 : RING_ROOM / (SLOT_U4 * 16);
     static_assert(2 * KS == OT, "both block kinds hold the same number of fragment groups");
+    static_assert(NSLOT >= 3, "three slots at least");
 };
 
 template <int N>
 __device__ __forceinline__ void handoff() {        // my part of the next block has landed; everyone is done with this one
-#ifdef SOC_K23_NO_BARRIER          // diagnostic build only (tools/experiments/k23_time.py, K23_EXTRA_FLAGS): what the ring would cost
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");         // WITHOUT its hand-off barrier -- results are wrong (races)
-#else
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-#endif
 }
 
-// DBG (diagnostics only) bit 0: no LDS-DMA inside the block loop, bit 1: no MFMA work (stream ceiling), bit 2: no fragment
-// reads after a piece's first group, bit 3: no activation.  PF: fragment groups read ahead.  STAG bit 0: waves 4..7 run one ring
-// piece behind waves 0..3, bit 1: the activation runs at raised wave priority, bit 2: the LDS-DMA instructions of a piece are
-// issued between the MFMA groups of the step instead of in front of them.
-// NW waves per workgroup: 8 (two per SIMD, 256 registers each) or 4 (one per SIMD, 512 registers: wider rows or more row tiles
-// per wave, so that a weight fragment read from LDS feeds more MFMAs).  RT row tiles per wave.
-template <int C, int ACT, bool HAS_LN, int NW, int RT, int NSLOT, int SB, int STAG, int PF, int DBG>
-__global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
+template <int C, int ACT, bool HAS_LN>
+__global__ __launch_bounds__(Geo<C>::NW * 64, Geo<C>::NW / 4) void mlp_split_kernel(
     const float* __restrict__ x, const u32x4* __restrict__ img, const float* __restrict__ b1, const float* __restrict__ b2,
     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, const float* __restrict__ res,
     const float* __restrict__ gamma2, const float* __restrict__ beta2, float eps2, float* __restrict__ out,
     float* __restrict__ out_sum, long M, int F, int nrg, int nfs, int res_ln) {
     using G = Geo<C>;
-    constexpr int THREADS = NW * 64;
+    constexpr int NW = G::NW, RT = G::RT, NSLOT = G::NSLOT, SB = G::SB, THREADS = NW * 64;
     // a block travels in SB ring pieces (a piece = a slot = one DMA round set): P LDS-DMA instructions per thread and piece
-    constexpr int KS = G::KS, OT = G::OT, BLKP = G::BLKP_U4, SLOT = BLKP / SB, P = SLOT / THREADS;
+    constexpr int KS = G::KS, OT = G::OT, BLKP = G::BLKP_U4, SLOT = G::SLOT_U4, P = SLOT / THREADS;
     static_assert(OT % SB == 0 && SLOT % THREADS == 0 && (SB == 1 || BLKP == G::BLK_U4), "pieces are whole fragment groups");
-    static_assert((STAG & 3) == 0 || NW == 8, "the stagger pairs the two waves of a SIMD");
-    constexpr int D = NSLOT - 1 - ((STAG & 1) ? 1 : 0);                       // pieces in flight ahead of the one being consumed
+    constexpr int D = NSLOT - 1;                                        // pieces in flight ahead of the one being consumed
     static_assert(D >= 1 && (D - 1) * P < 64, "ring depth");
     extern __shared__ __attribute__((aligned(16))) u32x4 lds[];
     u32x4* slots = lds;
@@ -114,19 +119,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                          ::"s"(dst + u * (THREADS * 16)), "v"(voff), "s"(src + u * (THREADS * 16)) : "memory");
     };
-    auto dma_one = [&](int piece, int slot, int u) {      // instruction u of a piece's P (STAG bit 2: spread between the MFMAs)
-        const char* src = ibase + (long)piece * (SLOT * 16);
-        const unsigned dst = lds_slots + (unsigned)slot * (SLOT * 16);
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                     ::"s"(dst + u * (THREADS * 16)), "v"(voff), "s"(src + u * (THREADS * 16)) : "memory");
-    };
     auto next_slot = [](int s) { return s + 1 == NSLOT ? 0 : s + 1; };
     __syncthreads();
     // One pass = up to 8 RT row tiles through the whole hidden range.  NRT (compile time) = this wave's tiles in the pass:
     // the accumulator updates are straight-line code for every count, a wave without tiles only feeds the ring.
-    auto pass = [&](auto nrt_c, auto late_c, long pt) {
+    auto pass = [&](auto nrt_c, long pt) {
         constexpr int NRT = decltype(nrt_c)::value;
-        constexpr bool LATE = decltype(late_c)::value;
         constexpr int NX = NRT > 0 ? NRT : 1;
         bf16x8 xb[NX][KS][3];
         float ln_mean[NX], ln_rstd[NX];         // kept for a residual that is LN(x) itself (res_ln: the encoder's norm1 folded in)
@@ -193,17 +191,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
         f32x4 acc1[NX][2];          // a chunk of the hidden layer between its two blocks: H^T tiles j = 0, 1, bias included
         bf16x8 hb[NX][3];           // ... and once activated and split: the B operand of the second product
         // ---- the two kinds of block, one ring piece (1 / SB of a block: NGS fragment groups) at a time.  Fragment groups are
-        // read PF groups ahead of the MFMAs that consume them.
+        // read one group ahead of the MFMAs that consume them.
         constexpr int NGS = OT / SB;
-        constexpr bool SPREAD = (STAG & 4) != 0 && NRT > 0 && !(DBG & 2);
-        int dq = -1, dsl = 0;                   // the piece whose LDS-DMA instructions this step still has to issue (SPREAD)
-        auto spread = [&](int gi) {             // instruction u goes out behind fragment group (u + 1) NGS / (P + 1) - 1
-            if constexpr (SPREAD) {
-#pragma unroll
-                for (int u = 0; u < P; ++u)
-                    if (gi == ((u + 1) * NGS) / (P + 1) && dq >= 0) dma_one(dq, dsl, u);
-            }
-        };
         auto frag = [&](bf16x8 (&wf)[3], const u32x4* wl, int gi) {
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) wf[pl] = __builtin_bit_cast(bf16x8, wl[(gi * 3 + pl) * 64]);
@@ -212,7 +201,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
         // (j, s) = (g / KS, g % KS), j = hidden tile
         auto first = [&](int blk, auto sb_c, int sl) {
             constexpr int sb = decltype(sb_c)::value;
-            if ((DBG & 2) || NRT == 0) return;
+            if (NRT == 0) return;
             const u32x4* wl = slots + sl * SLOT + lane;
             if (sb == 0) {      // the accumulators start from b1 (lane (r, kq) holds hidden columns 4 kq .. + 3 of each tile)
                 const f32x4* bp = reinterpret_cast<const f32x4*>(b1s + 16 * blk + 4 * kq);
@@ -220,41 +209,35 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
 #pragma unroll
                 for (int rt = 0; rt < NRT; ++rt) { acc1[rt][0] = bq0; acc1[rt][1] = bq1; }
             }
-            bf16x8 wf[PF + 1][3];
-#pragma unroll
-            for (int q = 0; q < PF; ++q) frag(wf[q], wl, q);
+            bf16x8 wf[2][3];
+            frag(wf[0], wl, 0);
 #pragma unroll
             for (int gi = 0; gi < NGS; ++gi) {
-                if (gi + PF < NGS && !((DBG & 4) && gi > 0)) frag(wf[(gi + PF) % (PF + 1)], wl, gi + PF);
+                if (gi + 1 < NGS) frag(wf[(gi + 1) & 1], wl, gi + 1);
                 const int g = sb * NGS + gi, j = g / KS, s = g % KS;
-                const int cur = (DBG & 4) ? 0 : gi % (PF + 1);
 #pragma unroll
-                for (int rt = 0; rt < NRT; ++rt) mfma6(acc1[rt][j], wf[cur], xb[rt][s][0], xb[rt][s][1], xb[rt][s][2]);
-                // the reads go out in front of this group's MFMAs; PF groups ahead, not all of them
-                if (gi + PF < NGS && !(DBG & 4)) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+                for (int rt = 0; rt < NRT; ++rt) mfma6(acc1[rt][j], wf[gi & 1], xb[rt][s][0], xb[rt][s][1], xb[rt][s][2]);
+                // the reads go out in front of this group's MFMAs; one group ahead, not all of them
+                if (gi + 1 < NGS) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 6 * NRT, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                spread(gi);
             }
         };
         // piece `sb` of a W2 block in slot `sl`: (activation and split of the chunk first), then its output tiles get the
         // chunk's 32 hidden columns
         auto second = [&](auto sb_c, int sl) {
             constexpr int sb = decltype(sb_c)::value;
-            if ((DBG & 2) || NRT == 0) return;
+            if (NRT == 0) return;
             const u32x4* wl = slots + sl * SLOT + lane;
-            bf16x8 wf[PF + 1][3];
-#pragma unroll
-            for (int q = 0; q < PF; ++q) frag(wf[q], wl, q);
+            bf16x8 wf[2][3];
+            frag(wf[0], wl, 0);
             if (sb == 0) {
-                if (STAG & 2) __builtin_amdgcn_s_setprio(1);   // the vector work goes in front of the partner wave's MFMAs
 #pragma unroll
                 for (int rt = 0; rt < NRT; ++rt) {
                     float v[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) v[i] = acc1[rt][i >> 2][i & 3];
-                    if (DBG & 8) {
-                    } else if (ACT == 1) {
+                    if (ACT == 1) {
 #pragma unroll
                         for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
                     } else {
@@ -264,27 +247,22 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
                     }
                     split8(v, hb[rt][0], hb[rt][1], hb[rt][2]);
                 }
-                if (STAG & 2) __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int gi = 0; gi < NGS; ++gi) {
-                if (gi + PF < NGS && !((DBG & 4) && gi > 0)) frag(wf[(gi + PF) % (PF + 1)], wl, gi + PF);
+                if (gi + 1 < NGS) frag(wf[(gi + 1) & 1], wl, gi + 1);
                 const int ot = sb * NGS + gi;
-                const int cur = (DBG & 4) ? 0 : gi % (PF + 1);
 #pragma unroll
-                for (int rt = 0; rt < NRT; ++rt) mfma6(acc2[rt][ot], wf[cur], hb[rt][0], hb[rt][1], hb[rt][2]);
-                if (gi + PF < NGS && !(DBG & 4)) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+                for (int rt = 0; rt < NRT; ++rt) mfma6(acc2[rt][ot], wf[gi & 1], hb[rt][0], hb[rt][1], hb[rt][2]);
+                if (gi + 1 < NGS) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 6 * NRT, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                spread(gi);
             }
         };
         if (nq >= D) handoff<(D - 1) * P>(); else handoff<0>();         // piece 0 has landed
-        // Ring step t: the piece D ahead goes out, a piece is consumed, the next one is waited for.  Waves 0..3 consume piece t;
-        // with the stagger (LATE) waves 4..7 consume piece t - 1, whose slot is `pslot`: on every SIMD one wave then starts a
-        // step with the activation (vector ALU, at raised priority) while its partner starts with MFMAs.
-        int slot = 0, pslot = 0, dslot = D % NSLOT, q = 0;
+        // Ring step q: the piece D ahead goes out, piece q is consumed, the next one is waited for.
+        int slot = 0, dslot = D % NSLOT, q = 0;
         // piece K of a chunk: K < SB -> W1 piece K, else W2 piece K - SB
         auto piece = [&](auto k_c, int blk, int sl) {
             constexpr int K_ = decltype(k_c)::value;
@@ -292,22 +270,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
             else second(std::integral_constant<int, K_ - SB>{}, sl);
         };
         auto step = [&](auto k_c, int blk) {
-            constexpr int K_ = decltype(k_c)::value;
             const bool more = q + D < nq;
-            if (!(DBG & 1) && more) {
-                if constexpr (SPREAD && !LATE) { dq = q + D; dsl = dslot; }
-                else dma(q + D, dslot);
+            if (more) {
+                dma(q + D, dslot);
                 dslot = next_slot(dslot);
-            } else {
-                dq = -1;
             }
-            if constexpr (!LATE) piece(k_c, blk, slot);
-            else if (K_ > 0) piece(std::integral_constant<int, (K_ > 0 ? K_ - 1 : 0)>{}, blk, pslot);
-            else if (blk > 0) piece(std::integral_constant<int, 2 * SB - 1>{}, blk - 2, pslot);
+            piece(k_c, blk, slot);
             if (q + 1 < nq) {
                 if (more) handoff<(D - 1) * P>(); else handoff<0>();
             }
-            pslot = slot;
             slot = next_slot(slot);
             ++q;
         };
@@ -325,7 +296,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
                 step(std::integral_constant<int, 7>{}, blk);
             }
         }
-        if constexpr (LATE) piece(std::integral_constant<int, 2 * SB - 1>{}, nb - 2, pslot);
         // ---- lane (r, kq) holds out[m][16 ot + 4 kq .. + 3] of its tiles.  b2 and the residual are added LAST, to the finished
         // sum of products (starting the accumulators from them would round every product at the residual's magnitude); the
         // loads of a tile go out together
@@ -397,19 +367,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_split_kernel(
     for (long pt = t0; pt < t1; pt += NW * RT) {
         if (pt != t0) handoff<0>();                 // nobody still reads the slots the next pass's prologue refills
         // this wave's row tiles: pt + NW rt + wave (a part-filled pass leaves the later tiles of a wave empty first)
+        static_assert(RT <= 2, "one pass instantiation per tile count");
         int nrt = 0;
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
             if (pt + NW * rt + wave < t1) nrt = rt + 1;
-        auto run = [&](auto late_c) {
-            if (RT >= 4 && nrt == 4) pass(std::integral_constant<int, RT >= 4 ? 4 : 0>{}, late_c, pt);
-            else if (RT >= 3 && nrt == 3) pass(std::integral_constant<int, RT >= 3 ? 3 : 0>{}, late_c, pt);
-            else if (RT >= 2 && nrt == 2) pass(std::integral_constant<int, RT >= 2 ? 2 : 0>{}, late_c, pt);
-            else if (nrt == 1) pass(std::integral_constant<int, 1>{}, late_c, pt);
-            else pass(std::integral_constant<int, 0>{}, late_c, pt);
+        auto run = [&](int n) {                     // the tile count becomes a compile-time constant of the pass
+            if (RT >= 2 && n == 2) pass(std::integral_constant<int, RT >= 2 ? 2 : 0>{}, pt);
+            else if (n == 1) pass(std::integral_constant<int, 1>{}, pt);
+            else pass(std::integral_constant<int, 0>{}, pt);
         };
-        if ((STAG & 1) && wave >= NW / 2) run(std::integral_constant<bool, (STAG & 1) != 0>{});
-        else run(std::false_type{});
+        run(nrt);
     }
     __syncthreads();        // the waves retire together
 }
@@ -541,19 +509,10 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const float* __restrict__
     }
 }
 
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
-
-// The shipped form of a width: waves per workgroup and row tiles per wave.  256-register waves (NW = 8) hold the x fragments
-// (3 C / 8 registers per tile) and the output accumulators (C / 4 per tile) of RT tiles up to C = 256; C = 384 needs the 512
-// registers of a one-wave-per-SIMD workgroup.
-constexpr int form_nw(int C) { return C > 256 ? 4 : 8; }
-constexpr int form_rt(int C) { return C <= 96 ? 2 : 1; }
-constexpr int tiles_per_pass(int C) { return form_nw(C) * form_rt(C); }
-
 template <int C>
-size_t lds_bytes(int nslot, int sb, int F, int nfs) {
+size_t lds_bytes(int F, int nfs) {       // the ring, gamma / beta, the b1 of the widest hidden range
     const int nc = (F / 32 + nfs - 1) / nfs;
-    return (size_t)nslot * (Geo<C>::BLKP_U4 / sb) * 16 + 8 * C + (size_t)nc * 128;
+    return (size_t)Geo<C>::NSLOT * Geo<C>::SLOT_U4 * 16 + 8 * C + (size_t)nc * 128;
 }
 
 struct Args {
@@ -568,68 +527,22 @@ struct Args {
     hipStream_t st;
 };
 
-template <int C, int ACT, bool HAS_LN, int NW, int RT, int NSLOT, int SB, int STAG, int PF, int DBG>
-int launch(const Args& a) {
-    const void* fn = reinterpret_cast<const void*>(mlp_split_kernel<C, ACT, HAS_LN, NW, RT, NSLOT, SB, STAG, PF, DBG>);
-    const size_t lds = lds_bytes<C>(NSLOT, SB, a.F, a.nfs);
-    if (lds > 160 * 1024) return SOC_EUNSUPPORTED;
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((mlp_split_kernel<C, ACT, HAS_LN, NW, RT, NSLOT, SB, STAG, PF, DBG>), dim3((unsigned)(a.nrg * a.nfs)),
-                       dim3(NW * 64), lds, a.st, a.x, a.img, a.b1, a.b2, a.gamma, a.beta, a.eps, a.res, a.gamma2, a.beta2, a.eps2,
-                       a.out, a.out_sum, a.M, a.F, a.nrg, a.nfs, a.res_ln);
-    return soc_check_launch();
-}
-
-// The ring of a width: a block of C <= 256 is one piece, three or four slots; the 72-KB blocks of C = 384 travel as halves (36 KB)
-// through four slots -- two whole-block slots would leave one block in flight, too little to cover the L2 latency.
-constexpr int form_sb(int C) { return C > 256 ? 2 : 1; }
-template <int C>
-constexpr int form_ns() {
-    constexpr int ns = (160 * 1024 - 8 * C - 4096) / (Geo<C>::BLKP_U4 / form_sb(C) * 16);     // slots beside a 1024-wide b1 range
-    return ns >= 4 ? 4 : ns;
-}
-
-// variant = NSLOT + 8 * log2(SB) + 32 * DBG + 512 * (PF - 1) + 1024 * STAG; 0 = the shipped choice for the width
 template <int C, int ACT, bool HAS_LN>
-int launch_variant(const Args& a, int variant) {
-    static_assert(form_ns<C>() >= 3, "three slots at least");
-    if (variant == 0) return launch<C, ACT, HAS_LN, form_nw(C), form_rt(C), form_ns<C>(), form_sb(C), 0, 1, 0>(a);
-#ifdef SOC_K23_VARIANTS         // diagnostic build (tools/experiments/k23_time.py)
-#define V(NS, LSB, ST, PFD, DB)                                                                                  \
-    case NS + 8 * LSB + 32 * DB + 512 * (PFD - 1) + 1024 * ST:                                                   \
-        if constexpr ((size_t)NS * (Geo<C>::BLKP_U4 >> LSB) * 16 + 8 * C + 4096 <= 160 * 1024 &&                 \
-                      (Geo<C>::OT >> LSB) >= 1 && (LSB == 0 || Geo<C>::BLKP_U4 == Geo<C>::BLK_U4) &&             \
-                      (Geo<C>::BLKP_U4 >> LSB) % (NW0 * 64) == 0 && ((ST & 3) == 0 || NW0 == 8))                       \
-            return launch<C, ACT, HAS_LN, NW0, RT0, NS, (1 << LSB), ST, PFD, DB>(a);                             \
-        else break;
-    constexpr int NW0 = form_nw(C), RT0 = form_rt(C);
-    switch (variant) {
-        V(2, 0, 0, 1, 0) V(3, 0, 0, 1, 0) V(4, 1, 0, 1, 0) V(3, 1, 0, 1, 0)
-        V(3, 0, 1, 1, 0) V(3, 0, 3, 1, 0) V(3, 0, 2, 1, 0) V(3, 0, 4, 1, 0) V(4, 0, 4, 1, 0) V(4, 1, 4, 1, 0) V(2, 0, 4, 1, 0)
-        V(3, 0, 0, 1, 1) V(3, 0, 0, 1, 2) V(3, 0, 0, 1, 13) V(4, 1, 0, 1, 1) V(4, 1, 0, 1, 2) V(4, 1, 0, 1, 13)
-        V(3, 1, 0, 1, 1) V(3, 1, 0, 1, 2) V(3, 1, 0, 1, 13) V(3, 1, 0, 1, 4) V(3, 1, 0, 1, 8) V(6, 2, 0, 1, 0) V(5, 2, 0, 1, 0) V(4, 2, 0, 1, 0)
-        default: break;
-    }
-#undef V
-#endif
-    return SOC_EUNSUPPORTED;
+int launch(const Args& a) {
+    const size_t lds = lds_bytes<C>(a.F, a.nfs);
+    if (lds > 160 * 1024) return SOC_EUNSUPPORTED;
+    if (soc_allow_lds<mlp_split_kernel<C, ACT, HAS_LN>>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
+    hipLaunchKernelGGL((mlp_split_kernel<C, ACT, HAS_LN>), dim3((unsigned)(a.nrg * a.nfs)), dim3(Geo<C>::NW * 64), lds, a.st, a.x,
+                       a.img, a.b1, a.b2, a.gamma, a.beta, a.eps, a.res, a.gamma2, a.beta2, a.eps2, a.out, a.out_sum, a.M, a.F,
+                       a.nrg, a.nfs, a.res_ln);
+    return soc_check_launch();
 }
 
 template <int C>
 int launch_c(const Args& a, int act, int variant) {
-#ifdef SOC_K23_VARIANTS         // the diagnostic build instantiates the forms the model uses only
-    if (act == 1 && !a.gamma) return launch_variant<C, 1, false>(a, variant);
-    if (act == 2 && a.gamma) return launch_variant<C, 2, true>(a, variant);
-#else
-    if (act == 1) return a.gamma ? launch_variant<C, 1, true>(a, variant) : launch_variant<C, 1, false>(a, variant);
-    if (act == 2) return a.gamma ? launch_variant<C, 2, true>(a, variant) : launch_variant<C, 2, false>(a, variant);
-#endif
+    if (variant != 0) return SOC_EUNSUPPORTED;      // one form per width ships; the diagnostic ones are gone
+    if (act == 1) return a.gamma ? launch<C, 1, true>(a) : launch<C, 1, false>(a);
+    if (act == 2) return a.gamma ? launch<C, 2, true>(a) : launch<C, 2, false>(a);
     return SOC_EUNSUPPORTED;
 }
 
@@ -699,7 +612,7 @@ static long tail_start(long M, int C, int cus) {
 // ring + gamma / beta + 4 bytes of b1 per hidden unit (lds_bytes above).
 template <int C>
 static int max_hidden() {
-    const size_t fixed = (size_t)form_ns<C>() * (Geo<C>::BLKP_U4 / form_sb(C)) * 16 + 8 * C;
+    const size_t fixed = (size_t)Geo<C>::NSLOT * Geo<C>::SLOT_U4 * 16 + 8 * C;
     return (int)((160 * 1024 - fixed) / 128) * 32;
 }
 
@@ -717,13 +630,13 @@ extern "C" int soc_mlp_split_max_hidden(int C) {
 
 extern "C" int soc_mlp_split_plan(long M, int C, int F, int* nrg_out, int* nfs_out, void* stream) {
     if (!width_ok(C) || F <= 0 || F % 32 != 0 || M <= 0 || !nrg_out || !nfs_out) return SOC_EUNSUPPORTED;
-    plan_rows(M, C, F, num_cus((hipStream_t)stream), nrg_out, nfs_out);
+    plan_rows(M, C, F, soc_num_cus((hipStream_t)stream), nrg_out, nfs_out);
     return SOC_OK;
 }
 
 extern "C" size_t soc_mlp_split_workspace_bytes(long M, int C, int F, void* stream) {
     if (!width_ok(C) || F <= 0 || F % 32 != 0 || M <= 0) return 0;
-    const int cus = num_cus((hipStream_t)stream);
+    const int cus = soc_num_cus((hipStream_t)stream);
     const long m0 = tail_start(M, C, cus);
     int nrg = 0, nfs = 0;
     plan_rows(m0 < M ? M - m0 : M, C, F, cus, &nrg, &nfs);
@@ -780,7 +693,7 @@ extern "C" int soc_mlp_split_f32(const float* x, const void* packed, const float
     if (M == 0) return SOC_OK;
     if (!width_ok(C) || F % 32 != 0) return SOC_EUNSUPPORTED;
     if (workspace_bytes < soc_mlp_split_workspace_bytes(M, C, F, stream)) return SOC_EWORKSPACE;
-    const int cus = num_cus((hipStream_t)stream);
+    const int cus = soc_num_cus((hipStream_t)stream);
     const long m0 = tail_start(M, C, cus);
     int nrg = 0, nfs = 0;
     if (m0 < M) {       // whole rounds first, then the tail over split hidden ranges

@@ -11,8 +11,6 @@
 // dims (keys) 16 s + 4 g + e of float4 reads, the same permutation on both operands, so every LDS read of Q / K / P is a
 // conflict-free ds_read_b128.  q / k / v / out are token-major [B, L, H * D] (what the projections produce: no transposes),
 // the mask is additive ([B, 1, Lq | 1, Lk] with the given strides, -inf on padding) or NULL.
-#include <atomic>
-
 #include "soc_common.h"
 
 namespace {
@@ -168,17 +166,8 @@ extern "C" int soc_small_attn_f32(const float* q, const float* k, const float* v
     const size_t lds = ((size_t)3 * LP * (D + 4) + (size_t)LP * (LP + 4) + (size_t)(mask ? (mask_query_stride ? L * L : L) : 0)) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     if (lds > 64 * 1024) {                                 // L > 48 at D = 64: above the default dynamic-LDS limit
-        static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-        const int dev = soc_current_device();
-        if (dev < 0) return SOC_ELAUNCH;
-        if (!attr_set[dev].load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(small_attn_kernel<64>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(small_attn_kernel<32>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-                return SOC_ELAUNCH;
-            attr_set[dev].store(true, std::memory_order_release);
-        }
+        if (soc_allow_lds<small_attn_kernel<64>>(96 * 1024) != SOC_OK || soc_allow_lds<small_attn_kernel<32>>(96 * 1024) != SOC_OK)
+            return SOC_ELAUNCH;
     }
     if (D == 64)
         hipLaunchKernelGGL(small_attn_kernel<64>, dim3((unsigned)(B * H)), dim3(NT), lds, st, q, k, v, mask, out, L, H, scale,

@@ -6,11 +6,15 @@
 namespace soc_split {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// a constant that must live in a VGPR: packed f32 instructions with an SGPR source are the victim form of the round-3
-// hardware interaction (tests/test_isa_rules.py checks the generated code)
+// A constant that must live in a VGPR.  Measured on MI355X (tools/experiments/pk_mfma_probe.hip): while a wave that mixes
+// bf16 MFMAs with LDS traffic is resident, packed f32 instructions (v_pk_fma_f32 ...) with an SGPR source return wrong low
+// halves in lanes 48..63.  Left alone the compiler feeds literal constants (the GELU polynomial, 1 / C, eps) to packed
+// instructions from SGPR pairs; passed through this opaque v_mov they stay vector operands (DESIGN.md section 3;
+// tests/test_isa_rules.py checks the generated code of every kernel file that uses these helpers).
 __device__ __forceinline__ float in_vgpr(float c) {
     float r;
     asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(c));
@@ -23,7 +27,8 @@ __device__ __forceinline__ GeluK gelu_k() {
             in_vgpr(1.421413741f), in_vgpr(-0.284496736f), in_vgpr(0.254829592f), in_vgpr(-1.4426950408889634f),
             in_vgpr(0.5f)};
 }
-// exact (erf) GELU as nn.GELU() computes it; erf by Abramowitz & Stegun 7.1.26 (|err| <= 1.5e-7), as K13 / K13b / K20
+// exact (erf) GELU as nn.GELU() computes it: 0.5 x (1 + erf(x / sqrt 2)), erf by Abramowitz & Stegun 7.1.26 (|err| <= 1.5e-7,
+// ~1 ulp of the 1 + erf it is added to), branch-free (libm's erff is piecewise); K13 (ws_linear.hip) has the f32 original
 __device__ __forceinline__ float gelu_erf(float x, const GeluK& k) {
     const float z = fabsf(x) * k.rs2;
     const float t = __builtin_amdgcn_rcpf(fmaf(k.a0, z, k.one));

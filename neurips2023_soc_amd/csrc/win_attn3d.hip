@@ -20,10 +20,10 @@
 //            token-major output with the inverse roll, dropping padded tokens.
 // MFMA work per (window, head): 2 * 25 * 25 * 8 = 10 000 instructions of 2048 FLOP.
 #include "soc_common.h"
+#include "split_math.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
-#include <atomic>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -40,7 +40,7 @@ constexpr int NT_MAX = 25;      // key / query tiles of 16 -> up to 400 tokens
 constexpr int NP_MAX = NT_MAX * 16;
 constexpr int THREADS = 512;    // 8 waves, 2 per SIMD
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace soc_split;       // f32x4, f32x16, bf16x8, u32x4, split8
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const float lds_cfloat;  // LDS-space pointer (ds_read, 32-bit address)
 
@@ -899,10 +899,8 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_full_kernel(
 //   * 392 queries = 12 tiles of 32 + 8: waves 0..3 take two tiles, waves 4..7 (their SIMD partners) one, and the 8-query
 //     tile is shared between waves 4..7 by key chunks, merged through LDS (as win_attn3d_full_kernel shares its 25th).
 // =============================================================================================
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int KROWB = 64;                          // bytes per plane row: 32 bf16
@@ -914,18 +912,7 @@ constexpr int SP_MISC = SP_V + 3 * PLANEB;         // wflag[8], gtab[25][4]
 constexpr size_t STREAM_LDS_BYTES = SP_MISC + 8 * 4 + FNT * 4 * 4 + 512;   // + slack behind the group table (the shared tile's row sums)
 static_assert(STREAM_LDS_BYTES <= 160 * 1024, "LDS");
 
-__device__ __forceinline__ void split8v(const float (&v)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a0 = (__bf16)v[i];
-        const float r1 = v[i] - (float)a0;
-        const __bf16 a1 = (__bf16)r1;
-        const float r2 = r1 - (float)a1;
-        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
-    }
-}
 __device__ __forceinline__ int swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }     // pi[(row >> 2) & 3]
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SNC = 13;                          // key chunks of 32 slots: 12 full + one with 8
 constexpr int SNQ = 13;                          // query tiles of 32: 12 full + one with 8
 constexpr int SCHB = 32 * KROWB;                 // bytes of a chunk in a plane
@@ -1188,11 +1175,11 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
                 const float vf[8] = {vv[it][0].x, vv[it][0].y, vv[it][0].z, vv[it][0].w, vv[it][1].x, vv[it][1].y, vv[it][1].z, vv[it][1].w};
                 bf16x8 h0, h1, h2;
                 char* dst = Kp + i * KROWB + ((c ^ swz(i)) << 4);
-                split8v(kf, h0, h1, h2);
+                split8(kf, h0, h1, h2);
                 *reinterpret_cast<bf16x8*>(dst) = h0;
                 *reinterpret_cast<bf16x8*>(dst + PLANEB) = h1;
                 *reinterpret_cast<bf16x8*>(dst + 2 * PLANEB) = h2;
-                split8v(vf, h0, h1, h2);
+                split8(vf, h0, h1, h2);
                 *reinterpret_cast<bf16x8*>(dst + 3 * PLANEB) = h0;
                 *reinterpret_cast<bf16x8*>(dst + 4 * PLANEB) = h1;
                 *reinterpret_cast<bf16x8*>(dst + 5 * PLANEB) = h2;
@@ -1665,23 +1652,12 @@ __global__ __launch_bounds__(THREADS, 2) void win_attn3d_stream_kernel(
     STAMP_RT(31);
 }
 
-// One launcher for every form: a <false> / <true> (shifted) kernel pair, each instantiation with its own per-device flag (the
-// dynamic-LDS attribute is device state, and a flag shared by two pairs would leave the second pair's attribute unset).
+// One launcher for every form: a <false> / <true> (shifted) kernel pair, both allowed their dynamic LDS before either runs.
 typedef void (*WinKernel)(const float*, const float*, const float*, float*, const WinParams);
 template <WinKernel K_PLAIN, WinKernel K_SHIFTED>
 int launch_pair(const float* qkv, const float* qkv_bias, const float* table, float* out,
                 const WinParams& p, long blocks, size_t lds, hipStream_t st) {
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(K_PLAIN),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(K_SHIFTED),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);   // idempotent: a racing thread just sets it again
-    }
+    if (soc_allow_lds<K_PLAIN>(160 * 1024) != SOC_OK || soc_allow_lds<K_SHIFTED>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
     hipLaunchKernelGGL((p.shifted ? K_SHIFTED : K_PLAIN), dim3((unsigned)blocks), dim3(THREADS), lds, st, qkv, qkv_bias,
                        table, out, p);
     return soc_check_launch();
@@ -1696,8 +1672,6 @@ int launch_nt(const float* qkv, const float* qkv_bias, const float* table, float
     return launch_pair<win_attn3d_kernel<NT, NT_PREV, false>, win_attn3d_kernel<NT, NT_PREV, true>>(
         qkv, qkv_bias, table, out, p, blocks, lds, st);
 }
-
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
 
 
 // ---------------------------------------------------------------------------------------------
@@ -1814,7 +1788,7 @@ extern "C" int soc_win_attn3d_f32(const float* qkv, const float* qkv_bias, const
     // the streaming bf16-split form: full 8x7x7 windows only; a launch argument, not process state
     const bool split = full_window && split_arith != 0;
     {
-        const Plan pl = plan_schedule(pairs, split ? SNQ : p.NT, num_cus((hipStream_t)stream), full_window, split);
+        const Plan pl = plan_schedule(pairs, split ? SNQ : p.NT, soc_num_cus((hipStream_t)stream), full_window, split);
         p.n_main = pl.n_main;
         p.qsplit = pl.qsplit;
     }

@@ -18,7 +18,6 @@
 //     its own set of workgroups, x re-read from L2).
 // out = act(LN(x) W^T + b) + residual, every part optional.
 #include "soc_common.h"
-#include <atomic>
 #include <math.h>
 
 namespace {
@@ -178,8 +177,6 @@ __global__ __launch_bounds__(THREADS, 2) void ws_linear_kernel(
     }
 }
 
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
-
 // columns of W per workgroup: even ranges, multiples of 16, that fit the LDS; 0 if N cannot be split that way
 int split_columns(int N, int K) {
     const int nc_max = (LDS_FLOATS / (K + 1)) & ~15;
@@ -191,18 +188,10 @@ int split_columns(int N, int K) {
 template <int K, int ACT, bool HAS_LN, bool HAS_RES, int CT>
 int launch_ct(const float* x, const float* gamma, const float* beta, float eps, const float* w, const float* bias,
                const float* res, float* out, long M, int N, hipStream_t st) {
-    const void* fn = reinterpret_cast<const void*>(ws_linear_kernel<K, ACT, HAS_LN, HAS_RES, CT>);
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];      // per instantiation and per device
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (soc_allow_lds<ws_linear_kernel<K, ACT, HAS_LN, HAS_RES, CT>>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
     const int nc_per_split = split_columns(N, K);
     const int nsplit = (N + nc_per_split - 1) / nc_per_split;
-    const int cus = num_cus(st);
+    const int cus = soc_num_cus(st);        // CUs the launch stream may use
     const long ntiles = (M + 15) >> 4;
     long per_split = cus / nsplit > 0 ? cus / nsplit : 1;
     if (per_split * 8 > ntiles) per_split = (ntiles + 7) / 8;         // never more waves than row tiles

@@ -16,54 +16,14 @@
 // The kernel mixes bf16 MFMAs with LDS traffic, so it follows the co-residence rule of DESIGN.md section 3: it claims all
 // 256 VGPRs, its waves retire behind a barrier, its packed f32 arithmetic uses VGPR operands only (tests/test_isa_rules.py).
 #include "soc_common.h"
-#include <atomic>
+#include "split_math.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace soc_split;
 constexpr int THREADS = 512;
 constexpr int LDS_BYTES = 152 * 1024;
-
-__device__ __forceinline__ float in_vgpr(float c) {
-    float r;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(c));
-    return r;
-}
-
-struct GeluK { float rs2, a0, one, c5, c4, c3, c2, c1, nlog2e, half; };
-__device__ __forceinline__ GeluK gelu_k() {
-    return {in_vgpr(0.70710678118654752f), in_vgpr(0.3275911f), in_vgpr(1.0f), in_vgpr(1.061405429f), in_vgpr(-1.453152027f),
-            in_vgpr(1.421413741f), in_vgpr(-0.284496736f), in_vgpr(0.254829592f), in_vgpr(-1.4426950408889634f),
-            in_vgpr(0.5f)};
-}
-// exact (erf) GELU, erf by Abramowitz & Stegun 7.1.26 as in K13 / K20; constants in VGPRs
-__device__ __forceinline__ float gelu_erf(float x, const GeluK& k) {
-    const float z = fabsf(x) * k.rs2;
-    const float t = __builtin_amdgcn_rcpf(fmaf(k.a0, z, k.one));
-    float p = fmaf(k.c5, t, k.c4);
-    p = fmaf(p, t, k.c3);
-    p = fmaf(p, t, k.c2);
-    p = fmaf(p, t, k.c1);
-    const float e = __builtin_amdgcn_exp2f(z * z * k.nlog2e);
-    const float erf_abs = fmaf(-p * t, e, k.one);
-    const float half = k.half * x;
-    return fmaf(half, copysignf(erf_abs, x), half);
-}
-
-// f32 x 8 -> three bf16 x 8 with a0 + a1 + a2 == a exactly
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const __bf16 a0 = (__bf16)v[i];
-        const float r1 = v[i] - (float)a0;
-        const __bf16 a1 = (__bf16)r1;
-        const float r2 = r1 - (float)a1;
-        h0[i] = a0; h1[i] = a1; h2[i] = (__bf16)r2;
-    }
-}
 
 // FLY (K > 256, no LayerNorm, one column group per row group): the rows are split step by step inside the MFMA loop instead
 // of up front -- K / 32 x 12 VGPRs of split operands would not fit beside the K / 4 raw words of a K = 384 / 512 row
@@ -243,8 +203,6 @@ __global__ __launch_bounds__(THREADS, 2) void ws_linear_split_kernel(
     __syncthreads();        // the waves retire together: no foreign wave beside a partner that still issues MFMAs
 }
 
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
-
 // columns of W per workgroup: even ranges, multiples of 16, whose three planes (+ bias) fit the LDS; 0 if impossible.
 // K > 256 (rows split step by step): a range is ONE group of 3, 2 or 1 column tiles.
 int split_columns(int N, int K) {
@@ -266,17 +224,10 @@ int launch_ct(const float* x, const float* gamma, const float* beta, float eps, 
     constexpr int RT = K <= 96 ? 2 : 1;
     constexpr bool FLY = K > 256;
     if (FLY && (HAS_LN || split_columns(N, K) / 16 != CT)) return SOC_EUNSUPPORTED;     // K13 takes those
-    const void* fn = reinterpret_cast<const void*>(ws_linear_split_kernel<K, ACT, HAS_LN, HAS_RES, CT, RT, FLY>);
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (soc_allow_lds<ws_linear_split_kernel<K, ACT, HAS_LN, HAS_RES, CT, RT, FLY>>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
     const int nc_per_split = split_columns(N, K);
     const int nsplit = (N + nc_per_split - 1) / nc_per_split;
-    const int cus = num_cus(st);
+    const int cus = soc_num_cus(st);        // CUs the launch stream may use
     const long ngroups = (M + 16 * RT - 1) / (16 * RT);
     long per_split = cus / nsplit > 0 ? cus / nsplit : 1;
     if (per_split * 8 > ngroups) per_split = (ngroups + 7) / 8;       // never more waves than row groups

@@ -4,7 +4,6 @@
 #pragma once
 #include "soc_common.h"
 #include "split_math.h"
-#include <atomic>
 #include <type_traits>
 
 namespace soc_xs {     // external linkage: the argument block crosses the two translation units
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(Geo<K>::NW * 64, Geo<K>::NW / 4) void xs_linear_ker
                 }
                 if (HAS_LN) {   // as nn.LayerNorm: two-pass mean / variance over the row, which lives in lanes (r, kq = 0..3)
                     // every rounding below is written out: left to contract on its own, the compiler rounded 0.07 % of the
-                    // normalised values one ulp apart between two instantiations (tools/experiments/k24_dbg.py), and a cut
+                    // normalised values one ulp apart between two instantiations (tools/experiments/README.md, round 5), and a cut
                     // must not change the bits
 #pragma clang fp contract(off)
                     const float inv_k = in_vgpr(1.0f / K), eps_v = in_vgpr(eps);
@@ -178,10 +177,8 @@ __global__ __launch_bounds__(Geo<K>::NW * 64, Geo<K>::NW / 4) void xs_linear_ker
                     // well as the others.  The first fragments go there as they are made (the row's f32 values still hold 192
                     // of the 256 others at that point); left to itself the allocator spilled six fragments here and re-loaded
                     // them at the top of every range of the span.
-#ifndef SOC_K24_NO_PIN          // diagnostic build: tools/experiments/k24_dbg.py
                     if (NW == 4 && s < (256 - 4 * NCT - 4) / 12)
                         asm volatile("" : "+a"(xb[s][0]), "+a"(xb[s][1]), "+a"(xb[s][2]));
-#endif
                 }
             }
         }
@@ -312,17 +309,12 @@ __global__ __launch_bounds__(256) void xs_pack_kernel(const float* __restrict__ 
     }
 }
 
-int num_cus(hipStream_t st) { return soc_num_cus(st); }      // CUs the launch stream may use (soc_capi.hip)
-
 using soc_xs::Args;
 
 // HBM traffic of the two workgroup -> XCD mappings (see the kernel): rows x gcd + 8 images / gcd against rows + 8 images.  The
 // second one needs the whole split image (6 B per weight) in an XCD's 4 MB L2 beside its share of the rows (the grid is
 // padded to whole groups of 8 row groups, one per XCD; surplus workgroups return at once).
 inline int xcd_rows_pays(long M, int N, int K, int nrg, int ncr) {
-#ifdef SOC_K24_NO_XCD_ROWS          // diagnostic build: the round-4 mapping everywhere (tools/experiments/k24_xcd_rows.py)
-    return 0;
-#endif
     if (ncr <= 1 || nrg < 8) return 0;
     const double x_bytes = 4.0 * (double)M * K, w_bytes = 6.0 * (double)N * K;
     if (w_bytes > 3.0 * 1024 * 1024) return 0;
@@ -334,16 +326,9 @@ inline int xcd_rows_pays(long M, int N, int K, int nrg, int ncr) {
 template <int K, int ACT, bool HAS_LN, int NCT>
 int launch(const Args& a) {
     using G = Geo<K>;
-    const void* fn = reinterpret_cast<const void*>(xs_linear_kernel<K, ACT, HAS_LN, NCT>);
     if ((size_t)a.rpw * NCT * 64 > (size_t)G::BIAS_BYTES) return SOC_EUNSUPPORTED;
     const size_t lds = (size_t)G::NSLOT * G::PIECE_U4 * 16 + 8 * K + (size_t)a.rpw * NCT * 64;
-    static std::atomic<bool> attr_set[SOC_MAX_DEVICES];
-    const int dev = soc_current_device();
-    if (dev < 0) return SOC_ELAUNCH;
-    if (!attr_set[dev].load(std::memory_order_acquire)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SOC_ELAUNCH;
-        attr_set[dev].store(true, std::memory_order_release);
-    }
+    if (soc_allow_lds<xs_linear_kernel<K, ACT, HAS_LN, NCT>>(160 * 1024) != SOC_OK) return SOC_ELAUNCH;
     const int xcd_rows = xcd_rows_pays(a.M, a.N, K, a.nrg, a.ncr);
     const int groups = xcd_rows ? (a.nrg + 7) / 8 * 8 : a.nrg;         // xcd_rows: whole groups of 8 row groups (one per XCD)
     hipLaunchKernelGGL((xs_linear_kernel<K, ACT, HAS_LN, NCT>), dim3((unsigned)(groups * a.ncr)), dim3(G::NW * 64), lds, a.st,

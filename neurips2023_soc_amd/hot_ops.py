@@ -1113,7 +1113,7 @@ def _mlp_packed(w1: Tensor, w2: Tensor) -> Tensor:
 
 def mlp_split(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, act: str = "gelu",
               ln: Optional[Tuple[Tensor, Tensor, float]] = None, residual: Optional[Tensor] = None,
-              out: Optional[Tensor] = None, cut: Optional[Tuple[int, int]] = None, variant: int = 0,
+              out: Optional[Tensor] = None, cut: Optional[Tuple[int, int]] = None,
               post_ln: Optional[Tuple[Tensor, Tensor, float]] = None, return_sum: bool = False, residual_ln: bool = False):
     """K23: LN2(act(LN(x) @ w1.T + b1) @ w2.T + b2 + residual) in one launch, the hidden layer in registers; ln / post_ln =
     (gamma, beta, eps) or None, act "relu" | "gelu".  With post_ln and return_sum the result is (sum in front of LN2, LN2(sum)).
@@ -1169,7 +1169,7 @@ def mlp_split(x: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, act: st
     with _timed("mlp_split", 4.0 * M * F_ * C_):
         rc = lib.soc_mlp_split_variant_f32(x.data_ptr(), packed.data_ptr(), b1c.data_ptr(), b2c.data_ptr(), ptr(g), ptr(be), eps,
                                            ptr(residual), ptr(g2), ptr(be2), eps2, out.data_ptr(), ptr(osum), ptr(ws), M, C_, F_,
-                                           _MLP_ACT[act], int(residual_ln), int(nrg), int(nfs), int(variant), _stream())
+                                           _MLP_ACT[act], int(residual_ln), int(nrg), int(nfs), 0, _stream())
     _lib.check(rc, "soc_mlp_split_variant_f32")
     return (osum, out) if return_sum else out
 

@@ -1,5 +1,6 @@
-"""K23 (mlp_split.hip) probe: numerics against f64 and the time of every diagnostic variant (ring depth, compute-only and
-stream-only ceilings) on the model's shapes.  Builds its own library with -DSOC_K23_VARIANTS:
+"""K23 (mlp_split.hip) probe: numerics against f64 and the time of the shipped form per cut on the model's shapes.  Builds
+its own library (the diagnostic variants it once timed -- ring depth, compute-only and stream-only ceilings -- were last in
+commit fc20909; their numbers are in tools/experiments/README.md):
 
     python tools/experiments/k23_time.py --build        (here: hipcc cross-compiles)
     python tools/experiments/k23_time.py [--quick]      (GPU box)
@@ -18,8 +19,7 @@ CSRC = os.path.join(ROOT, "neurips2023_soc_amd", "csrc")
 
 def build():
     os.makedirs(BUILD, exist_ok=True)
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17", "-DSOC_K23_VARIANTS",
-           *os.environ.get("K23_EXTRA_FLAGS", "").split(),
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17",
            "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-o", LIB, os.path.join(CSRC, "mlp_split.hip"),
            os.path.join(CSRC, "soc_capi.hip")]
     print(" ".join(cmd), flush=True)
@@ -59,7 +59,7 @@ def t(fn, reps=20):
     return 1e3 * s.elapsed_time(e) / reps
 
 
-def case(name, M, Cw, F, act, ln, res, cuts, variants):
+def case(name, M, Cw, F, act, ln, res, cuts):
     x = torch.randn(M, Cw, generator=g).cuda()
     w1 = (torch.randn(F, Cw, generator=g) / Cw ** 0.5).cuda()
     b1 = torch.randn(F, generator=g).cuda()
@@ -92,41 +92,29 @@ def case(name, M, Cw, F, act, ln, res, cuts, variants):
         else:
             nrg, nfs = cut
         ws = torch.empty(nfs * M * Cw, dtype=torch.float32, device="cuda") if nfs > 1 else None
-        for v in variants:
-            def run():
-                return lib.soc_mlp_split_variant_f32(x.data_ptr(), packed.data_ptr(), b1.data_ptr(), b2.data_ptr(), ptr(gam),
-                                                     ptr(bet), 1e-5, ptr(r), None, None, 0.0, out.data_ptr(), None, ptr(ws), M, Cw, F,
-                                                     1 if act == "relu" else 2, 0, nrg, nfs, v, st)
-            out.zero_()
-            rc = run()
-            if rc != 0:
-                print(f"{name} cut ({nrg},{nfs}) variant {v}: rc {rc}")
-                continue
-            torch.cuda.synchronize()
-            err = (out.double() - ref).abs().max().item() / scale
-            us = t(run, 10 if quick else 20)
-            dbg = (v >> 5) & 15
-            tag = f"  NS={v & 7} SB={1 << ((v >> 3) & 3)} PF={((v >> 9) & 1) + 1} STAG={v >> 10}" + ("" if not dbg else "  [wrong on purpose:" + "".join(
-                n for b, n in ((1, " no DMA in loop"), (2, " no MFMA"), (4, " no fragment reads"), (8, " no activation")) if dbg & b) + "]")
-            print(f"{name} M={M} C={Cw} F={F} cut ({nrg},{nfs}) variant {v:3d}: {us:7.1f} us  {fl / us / 1e6:6.1f} TFLOP/s  "
-                  f"max err / max|ref| {err:.2e}{tag}", flush=True)
+
+        def run():
+            return lib.soc_mlp_split_variant_f32(x.data_ptr(), packed.data_ptr(), b1.data_ptr(), b2.data_ptr(), ptr(gam),
+                                                 ptr(bet), 1e-5, ptr(r), None, None, 0.0, out.data_ptr(), None, ptr(ws), M, Cw, F,
+                                                 1 if act == "relu" else 2, 0, nrg, nfs, 0, st)
+        out.zero_()
+        rc = run()
+        if rc != 0:
+            print(f"{name} cut ({nrg},{nfs}): rc {rc}")
+            continue
+        torch.cuda.synchronize()
+        err = (out.double() - ref).abs().max().item() / scale
+        us = t(run, 10 if quick else 20)
+        print(f"{name} M={M} C={Cw} F={F} cut ({nrg},{nfs}): {us:7.1f} us  {fl / us / 1e6:6.1f} TFLOP/s  "
+              f"max err / max|ref| {err:.2e}", flush=True)
     return x, w1, b1, w2, b2, gam, bet, r, ref, scale
 
 
-def vr(ns=3, lsb=0, stag=0, pf=1, dbg=0):
-    return ns + 8 * lsb + 32 * dbg + 512 * (pf - 1) + 1024 * stag
-
-
-V = [0, vr(3), vr(3, stag=4), vr(2, stag=4)]
-if "--enc-only" in sys.argv:         # round 6: the encoder form with and without its hand-off barrier (K23_EXTRA_FLAGS=-DSOC_K23_NO_BARRIER)
-    case("enc", 32768, 256, 2048, "relu", False, True, [(256, 1)], [0, vr(3, dbg=13), vr(3, dbg=1), vr(3, dbg=4)])
-    case("s0", 115200, 96, 384, "gelu", True, True, [(256, 1)], [0])
-    case("s2", 7360, 384, 1536, "gelu", True, True, [None], [0])
+case("enc", 32768, 256, 2048, "relu", False, True, [(256, 1)])
+case("s0", 115200, 96, 384, "gelu", True, True, [(256, 1)])
+case("s2", 7360, 384, 1536, "gelu", True, True, [None])
+if "--enc-only" in sys.argv:
     sys.exit(0)
-case("enc", 32768, 256, 2048, "relu", False, True, [(256, 1)], V)
-case("s0", 115200, 96, 384, "gelu", True, True, [(256, 1)], [0, vr(3), vr(3, stag=4), vr(4, stag=4)])
-case("s1", 28800, 192, 768, "gelu", True, True, [None], V)
-case("s2", 7360, 384, 1536, "gelu", True, True, [None], [0, vr(4, 1), vr(4, 1, stag=4)])
-# Swin-B stage 2 (C = 512): the shipped form (three half-block slots), its ceilings, quarter-block pieces through 4 / 5 / 6 slots
-case("s2b", 7360, 512, 2048, "gelu", True, True, [None, (115, 1), (115, 4)],
-     [0, vr(3, 1), vr(3, 1, dbg=1), vr(3, 1, dbg=2), vr(3, 1, dbg=4), vr(3, 1, dbg=8), vr(3, 1, dbg=13), vr(4, 2), vr(5, 2), vr(6, 2)])
+case("s1", 28800, 192, 768, "gelu", True, True, [None])
+# Swin-B stage 2 (C = 512): the planned cut, one hidden range, four ranges
+case("s2b", 7360, 512, 2048, "gelu", True, True, [None, (115, 1), (115, 4)])
