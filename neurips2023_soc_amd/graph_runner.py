@@ -8,26 +8,22 @@ captured like any other node.  Shapes are static per runner; build one runner pe
 """
 from __future__ import annotations
 
+import functools
+import os
 from typing import Dict, Optional
 
 import torch
 
 from . import clip_parallel as CP
 from . import hot_ops
-from . import postprocessing as P
 from .derived_cache import keep_alive
 from .nested_tensor import NestedTensor
 
 
-# Diagnostic switches read from the environment (gathered here; bench.py records every one that is set).  The
-# first four are read while a graph is CAPTURED and change what is captured; none of them changes results beyond f32 rounding.
+# Diagnostic switches read from the environment (gathered here; bench.py records every one that is set).  None of them
+# is read while a graph is captured: what a runner captures does not depend on the environment.
 SWITCHES = {
     "SOC_PIPELINE": "one-graph | two-stream: which software pipeline pipeline_class() returns (default one-graph)",
-    "SOC_NO_PLACE": "1: the head's two large hand-over tensors are copied into the static state instead of produced there",
-    "SOC_TAIL_ROW_FUSION": "1: the pipelined tail keeps K16's fused row chains (default: K7's small workgroups beside a head)",
-    "SOC_TAIL_NO_FORK": "1: the tail never forks FPN || query chain, not even in the drain graph",
-    "SOC_TAIL_PRIORITY": "0: the tail branch of the one-graph pipeline is captured at default stream priority (default: high)",
-    "SOC_GROUP_SEQ_FIRST": "1: a launch group keeps the reference's '(t h w) b c' / [T,B,...] layouts (a permute copy of every level each way)",
     "SOC_K24_SPANS": "0: K24 plans one column range per workgroup (the cut of round 4) instead of spans of ranges",
     "SOC_MATMUL": "split | f32: arithmetic a model is built with (hot_ops.DEFAULT_MATMUL_MODE; SOC.matmul_mode overrides per model)",
     "SOC_SPLIT_OFF": "comma list of call sites / kernels forced back to the f32 path (k1, k13, k24, mlp, swin, gelu, ...)",
@@ -37,7 +33,6 @@ SWITCHES = {
 
 def switches_set() -> Dict[str, str]:
     """The diagnostic switches that are set in this process's environment (empty in a default run)."""
-    import os
     return {k: os.environ[k] for k in list(SWITCHES) + ["SOC_PNG_LEVEL"] if os.environ.get(k) not in (None, "")}
 
 
@@ -54,8 +49,6 @@ def _holds_what_it_captures(init):
     -- geometry constants, packed weight images, workspaces; the captured graphs have their addresses baked in -- is appended
     to `self._held` and so stays allocated for exactly as long as the runner object lives (derived_cache.keep_alive), whatever
     the caches do with their entries later.  Evicting the runner (ClipInferencer) releases it.  Nothing of this runs on replay."""
-    import functools
-
     @functools.wraps(init)
     def wrapped(self, *args, **kwargs):
         self._held = []
@@ -64,70 +57,111 @@ def _holds_what_it_captures(init):
     return wrapped
 
 
-class ClipGraph:
+def capture(body, stream=None):
+    """body() captured into a graph of its own (on `stream`, else on a capture stream of torch's)."""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=stream, capture_error_mode=CAPTURE_MODE):
+        body()
+    return g
+
+
+def warm_up(body, device, side=None):
+    """body() on a side stream, off the capture (lazy inits, algorithm finds, packed weight images); the device is idle after."""
+    cur = torch.cuda.current_stream(device)
+    side = side or torch.cuda.Stream(device=device)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        body()
+    cur.wait_stream(side)
+    torch.cuda.synchronize(device)
+
+
+class _ClipRunner:
+    """What every runner shares: the static inputs of CLIPS clips, how they are staged, and an __init__ that builds inside the
+    keep-alive scope.  A runner class adds _build(warmup) -- its warm-up and captures -- and replay()."""
+
     CLIPS = 1              # clips per replay
 
     @_holds_what_it_captures
     def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
-        self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
-        self.device = torch.device(device)
-        self.clip = torch.zeros(T, 1, 3, H, W, device=self.device)
-        self.pad = torch.zeros(T, 1, H, W, dtype=torch.bool, device=self.device)
-        self.ids = torch.ones(1, L, dtype=torch.long, device=self.device)
-        self.attn = torch.ones(1, L, dtype=torch.long, device=self.device)
-        self.targets = [[{"size": (H, W)}] for _ in range(T)]
-        Q = model.num_queries
-        hm, wm = -(-H // 4), -(-W // 4)
-        self.record = torch.zeros(CP.record_size(T, Q, hm, wm), device=self.device)
-        self.out: Optional[Dict[str, torch.Tensor]] = None
-        self.graph = torch.cuda.CUDAGraph()
+        self._allocate(model, T, H, W, L, device)
         assert not hot_ops.op_profile.active(), "do not capture while kernel profiling is on"
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):  # warm-up off the capture: lazy inits, algorithm finds
-            for _ in range(warmup):
-                self._forward()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        with torch.cuda.graph(self.graph, capture_error_mode=CAPTURE_MODE):
-            self.out = self._forward()
+        self._build(warmup)
 
-    def _forward(self):
-        samples = NestedTensor(self.clip, self.pad, unpadded=True)  # static all-False pad mask
-        out = self.model(samples, None, {"input_ids": self.ids, "attention_mask": self.attn}, self.targets)
-        hot_ops.select_pack(out["pred_cls"], out["pred_masks"], self.record[None])      # K26 (was select_trajectory + pack_record)
-        return out
+    def _allocate(self, model, T: int, H: int, W: int, L: int, device) -> None:
+        self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
+        dev = self.device = torch.device(device)
+        n = self.CLIPS
+        # stored clip-major: the backbone's '(b t)' flatten of the [T,B,...] samples is then a view, not an 88 MB copy per replay
+        # (for one clip the two layouts are the same memory)
+        self.clip = torch.zeros(n, T, 3, H, W, device=dev).transpose(0, 1)
+        self.pad = torch.zeros(n, T, H, W, dtype=torch.bool, device=dev).transpose(0, 1)       # static all-False pad mask
+        self.ids = torch.ones(n, L, dtype=torch.long, device=dev)
+        self.attn = torch.ones(n, L, dtype=torch.long, device=dev)
+        self._masked = set()                                              # slots whose static attention mask is not all ones
+        self.targets = [[{"size": (H, W)}] for _ in range(T)]              # of ONE clip: the tail of a group runs per clip
+        hm, wm = -(-H // 4), -(-W // 4)
+        records = torch.zeros(n, CP.record_size(T, model.num_queries, hm, wm), device=dev)
+        self.record = records if n > 1 else records[0]
 
-    def run(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None,
-            attn: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """clip [T,3,H,W] or [T,1,3,H,W] on the device; ids / attn [1,L] token ids and attention mask (ones
-        when omitted); returns the static output dict (valid until the next run) -- `self.record` holds the
-        packed (query, scores, selected masks) result."""
+    def _samples(self):
+        return NestedTensor(self.clip, self.pad, unpadded=True)
+
+    def _tokens(self):
+        return {"input_ids": self.ids, "attention_mask": self.attn}
+
+    def stage_inputs(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None, attn: Optional[torch.Tensor] = None,
+                     slot: int = 0) -> None:
+        """Copy ONE clip [T,3,H,W] (or [T,1,3,H,W]) and its token ids / attention mask [1,L] or [L] into slot `slot`
+        (0 .. CLIPS - 1) of the static buffers, on the current stream; the mask is ones when omitted, and ids=None leaves both
+        as they are.  After this call the caller's `clip` may be overwritten by work ordered behind it -- a streaming feeder
+        releases its device slot here, not after the replay (clip_io.DoubleBufferedH2D)."""
+        dst = self.clip[:, slot]
+        dst.copy_(clip.view(dst.shape), non_blocking=True)
+        if ids is None:
+            return
+        self.ids[slot].copy_(ids.view(-1), non_blocking=True)
+        if attn is not None:
+            self.attn[slot].copy_(attn.view(-1), non_blocking=True)
+            self._masked.add(slot)
+        elif slot in self._masked:       # the static mask is all ones until a caller stages another one: no launch otherwise
+            self.attn[slot].fill_(1)
+            self._masked.discard(slot)
+
+    def run(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None, attn: Optional[torch.Tensor] = None):
+        """stage_inputs + replay: see the class for what a replay returns."""
         self.stage_inputs(clip, ids, attn)
         return self.replay()
 
-    def stage_inputs(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None,
-                     attn: Optional[torch.Tensor] = None) -> None:
-        """Copy the inputs into the graph's static buffers (on the current stream).  After this call the caller's `clip`
-        may be overwritten by work ordered behind it -- a streaming feeder releases its device slot here, not after the
-        replay (clip_io.DoubleBufferedH2D)."""
-        self.clip.copy_(clip.view(self.clip.shape), non_blocking=True)
-        if ids is not None:
-            self.ids.copy_(ids.view(self.ids.shape), non_blocking=True)
-            if attn is None:
-                if not getattr(self, "_attn_ones", True):   # the static mask is all ones until a caller stages another one
-                    self.attn.fill_(1)
-                    self._attn_ones = True
-            else:
-                self.attn.copy_(attn.view(self.attn.shape), non_blocking=True)
-                self._attn_ones = False
+
+class ClipGraph(_ClipRunner):
+    """The whole forward of one clip + query selection as one graph.  run(clip [T,3,H,W] or [T,1,3,H,W] on the device, ids / attn
+    [1,L]) returns the static output dict (valid until the next run); `self.record` holds the packed (query, scores, selected
+    masks) result."""
+
+    def _build(self, warmup: int) -> None:
+        self.out: Optional[Dict[str, torch.Tensor]] = None
+
+        def warm():
+            for _ in range(warmup):
+                self._forward()
+
+        def forward():
+            self.out = self._forward()
+        warm_up(warm, self.device)
+        self.graph = capture(forward)
+
+    def _forward(self):
+        out = self.model(self._samples(), None, self._tokens(), self.targets)
+        hot_ops.select_pack(out["pred_cls"], out["pred_masks"], self.record[None])      # K26 (was select_trajectory + pack_record)
+        return out
 
     def replay(self) -> Dict[str, torch.Tensor]:
         self.graph.replay()
         return self.out
 
 
-class PipelinedClipGraph:
+class PipelinedClipGraph(_ClipRunner):
     """Two clips in flight inside ONE stream of graph replays (software pipeline across clips).
 
     Graph k runs the TAIL of the previous clip (FPN, query decoder, VOC, heads, mask head, selection -- ~120 short,
@@ -139,99 +173,80 @@ class PipelinedClipGraph:
     their order are those of ClipGraph; only which clips' kernels share the GPU changes.
 
         for clip in clips:
-            rec = g.run(clip, ids)        # packed record of the clip submitted one call earlier, or None
+            rec = g.run(clip, ids)        # self.record if this replay finished the clip submitted one call earlier (copy it out
+                                          # before the next call), else None
         rest = g.flush()                  # list with the record (a clone) of the clip still in flight
     """
 
     DEPTH = 2
-    CLIPS = 1              # clips per replay (PairPipelinedClipGraph: 2)
 
-    @_holds_what_it_captures
-    def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
-        self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
-        dev = self.device = torch.device(device)
-        self.clip = torch.zeros(T, 1, 3, H, W, device=dev)
-        self.pad = torch.zeros(T, 1, H, W, dtype=torch.bool, device=dev)
-        self.ids = torch.ones(1, L, dtype=torch.long, device=dev)
-        self.attn = torch.ones(1, L, dtype=torch.long, device=dev)
-        self.targets = [[{"size": (H, W)}] for _ in range(T)]
-        hm, wm = -(-H // 4), -(-W // 4)
-        self.record = torch.zeros(CP.record_size(T, model.num_queries, hm, wm), device=dev)
-        assert not hot_ops.op_profile.active(), "do not capture while kernel profiling is on"
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+    def _build(self, warmup: int) -> None:
+        dev = self.device
+
+        def warm():
             for _ in range(max(warmup, 1)):
                 sb = self._head(fork=False)
                 self._tail(sb, fork=False)
             # static, double-buffered hand-over state (only what changes from clip to clip is copied; geometry
             # constants are shared)
             self.sb = [self._clone(sb), self._clone(sb)]
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
+        warm_up(warm, dev)
         # The tail branch is captured from a HIGH-priority stream: its short launches are taken first whenever a CU frees up
-        # beside the head's chip-filling kernels (measured on one box, alternating: 6.31 -> 6.24 ms per clip;
-        # SOC_TAIL_PRIORITY=0 restores the default-priority branch)
-        import os
-        self._pc = torch.cuda.Stream(device=dev, priority=0 if os.environ.get("SOC_TAIL_PRIORITY", "1") == "0" else -1)
+        # beside the head's chip-filling kernels (measured on one box, alternating: 6.31 ms per clip from a default-priority stream, 6.24 from this one)
+        self._pc = torch.cuda.Stream(device=dev, priority=-1)
 
-        def capture(body):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                body()
-            return g
+        def placed_head(k):
+            """The head with its two largest hand-over tensors -- the stage-0 token map (44 MB at the BASELINE size) and the
+            encoder memory (40 MB) -- produced IN sb[k]; the few small ones are stored behind it."""
+            self._store(self._placed(lambda: self._head(fork=True), self.sb[k], ("swin0", "encoder_memory")), self.sb[k])
 
         def tail_beside_head(k):
             cur = torch.cuda.current_stream(dev)
             self._pc.wait_stream(cur)
             with torch.cuda.stream(self._pc):
                 self._tail(self.sb[1 - k], fork=False)          # clip i-1
-            self._store(self._placed_head(self.sb[k]), self.sb[k])      # clip i
+            placed_head(k)                                       # clip i
             cur.wait_stream(self._pc)
 
         self.steady = [capture(lambda k=k: tail_beside_head(k)) for k in (0, 1)]
         self.drain = [capture(lambda k=k: self._tail(self.sb[k], fork=True)) for k in (0, 1)]
         # the first replay after a flush has no tail to run: head only, into sb[0] (a steady graph there would run the tail of
         # stale state beside it)
-        self.first = capture(lambda: self._store(self._placed_head(self.sb[0]), self.sb[0]))
+        self.first = capture(lambda: placed_head(0))
         self._n = 0            # clips submitted since the last flush
 
     # -- stages ------------------------------------------------------------------------------------------
     def _head(self, fork: bool):
-        samples = NestedTensor(self.clip, self.pad, unpadded=True)
-        sa = self.model.forward_backbone(samples, None, {"input_ids": self.ids, "attention_mask": self.attn})
+        sa = self.model.forward_backbone(self._samples(), None, self._tokens())
         return self.model.forward_fuse_encode(sa, fork=fork)
 
-    def _placed_head(self, dst):
-        """The head with its two largest hand-over tensors -- the stage-0 token map (44 MB at the BASELINE size) and the encoder
-        memory (40 MB) -- produced IN the static state `dst` (hot_ops.place_output) instead of copied there behind the head."""
+    def _placed(self, body, dst, tags):
+        """`body()` with its large outputs named in `tags` -- "swin0": the stage-0 token map, "encoder_memory" -- produced IN the
+        static state `dst` (hot_ops.place_output) instead of copied there behind it."""
         f0, mem = dst["feats0"], dst["ctx"][0]
         n, c, h, w = f0.shape
         tok = f0.permute(0, 2, 3, 1)                     # '(b t) h w c': the layout the stage writes
-        import os
-        if os.environ.get("SOC_NO_PLACE", "0") == "1":  # diagnostic: the copies of round 3
-            return self._head(fork=True)
         try:
-            if tok.is_contiguous():
+            if "swin0" in tags and tok.is_contiguous():
                 hot_ops.place_output("swin0", tok.view(n // self.T, self.T, h, w, c))
-            if mem.is_contiguous():
+            if "encoder_memory" in tags and mem.is_contiguous():
                 hot_ops.place_output("encoder_memory", mem)
-            return self._head(fork=True)
+            return body()
         finally:
-            hot_ops.place_output("swin0", None)
-            hot_ops.place_output("encoder_memory", None)
+            for tag in tags:
+                hot_ops.place_output(tag, None)
 
     def _tail(self, sb, fork: bool):
         # the tail runs beside another clip's head, which pays for the tail's CU time and not for its launch count: the
         # query chain keeps K7's small workgroups here (hot_ops.row_chain_fusion)
-        import os
-        prev, hot_ops.row_chain_fusion = hot_ops.row_chain_fusion, os.environ.get("SOC_TAIL_ROW_FUSION", "0") == "1"
-        if os.environ.get("SOC_TAIL_NO_FORK", "0") == "1":
-            fork = False
+        prev, hot_ops.row_chain_fusion = hot_ops.row_chain_fusion, False
         try:
-            out = self.model.forward_tail(sb, self.targets, fork=fork)
+            self._tail_body(sb, fork)
         finally:
             hot_ops.row_chain_fusion = prev
+
+    def _tail_body(self, sb, fork: bool):
+        out = self.model.forward_tail(sb, self.targets, fork=fork)
         hot_ops.select_pack(out["pred_cls"], out["pred_masks"], self.record[None])      # K26
 
     _VARY = ("ctx", "feats0", "lang_last", "word_pad", "sentence")    # what the head hands to the tail per clip
@@ -258,7 +273,7 @@ class PipelinedClipGraph:
         pairs = []
 
         def put(d, t):
-            if d.data_ptr() != t.data_ptr():             # else: already produced in place (_placed_head)
+            if d.data_ptr() != t.data_ptr():             # else: already produced in place (_placed)
                 pairs.append((d, t))
 
         for k in self._VARY:
@@ -282,14 +297,6 @@ class PipelinedClipGraph:
             torch._foreach_copy_([d for d, _ in group], [t for _, t in group])
 
     # -- driving -----------------------------------------------------------------------------------------
-    def run(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None, attn: Optional[torch.Tensor] = None):
-        """Submit `clip`.  Returns self.record if this replay finished the clip submitted one call earlier
-        (copy it out before the next call), else None."""
-        self.stage_inputs(clip, ids, attn)
-        return self.replay()
-
-    stage_inputs = ClipGraph.stage_inputs
-
     def replay(self):
         (self.first if self._n == 0 else self.steady[self._n % 2]).replay()
         self._n += 1
@@ -331,45 +338,25 @@ class TwoStreamClipGraph(PipelinedClipGraph):
     call earlier, flush() drains.
     """
 
-    @_holds_what_it_captures
-    def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
-        self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
-        dev = self.device = torch.device(device)
-        self.clip = torch.zeros(T, 1, 3, H, W, device=dev)
-        self.pad = torch.zeros(T, 1, H, W, dtype=torch.bool, device=dev)
-        self.ids = torch.ones(1, L, dtype=torch.long, device=dev)
-        self.attn = torch.ones(1, L, dtype=torch.long, device=dev)
-        self.targets = [[{"size": (H, W)}] for _ in range(T)]
-        hm, wm = -(-H // 4), -(-W // 4)
-        self.record = torch.zeros(CP.record_size(T, model.num_queries, hm, wm), device=dev)
-        assert not hot_ops.op_profile.active(), "do not capture while kernel profiling is on"
+    def _build(self, warmup: int) -> None:
+        dev = self.device
         self.main, self.aux = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-        caller = torch.cuda.current_stream(dev)
-        self.main.wait_stream(caller)
-        with torch.cuda.stream(self.main):      # warm-up off the capture: lazy inits, algorithm finds, packed weight images
+
+        def warm():
             for _ in range(max(warmup, 1)):
                 tx = self._text()
                 sb = self._fuse(self._video(), tx)
                 self._tail(sb, fork=False)
             self.tx = [self._clone_text(tx), self._clone_text(tx)]
             self.sb = [self._clone(sb), self._clone(sb)]
-        self.aux.wait_stream(self.main)
-        caller.wait_stream(self.main)
-        torch.cuda.synchronize(dev)
-
-        def capture(body, stream):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=stream, capture_error_mode=CAPTURE_MODE):
-                body()
-            return g
-
+        warm_up(warm, dev, self.main)
         self._vs = [None, None]
 
         def video(k):       # Video-Swin of clip i, its stage-0 token map produced IN sb[k]
-            self._vs[k] = self._placed(lambda: self._video(), self.sb[k], "swin0")
+            self._vs[k] = self._placed(self._video, self.sb[k], ("swin0",))
 
         def fuse(k):        # fusion + encoder of clip i: reads Video-Swin's static outputs and tx[k], fills sb[k]
-            st = self._placed(lambda: self._fuse(self._vs[k], self.tx[k]), self.sb[k], "encoder_memory")
+            st = self._placed(lambda: self._fuse(self._vs[k], self.tx[k]), self.sb[k], ("encoder_memory",))
             self._store(st, self.sb[k])
 
         def text(k):
@@ -391,28 +378,13 @@ class TwoStreamClipGraph(PipelinedClipGraph):
     _TEXT = ("words", "word_pad", "text_pos", "sentence")
 
     def _text(self):
-        return self.model.forward_text_state({"input_ids": self.ids, "attention_mask": self.attn}, self.device)
+        return self.model.forward_text_state(self._tokens(), self.device)
 
     def _video(self):
-        return self.model.forward_video(NestedTensor(self.clip, self.pad, unpadded=True))
+        return self.model.forward_video(self._samples())
 
     def _fuse(self, vs, tx):
         return self.model.forward_fuse_encode({**vs, **tx}, fork=False)
-
-    def _placed(self, body, dst, tag):
-        """`body()` with one of its large outputs produced IN the static state (hot_ops.place_output) instead of copied there."""
-        f0, mem = dst["feats0"], dst["ctx"][0]
-        try:
-            if tag == "swin0":
-                n, c, h, w = f0.shape
-                tok = f0.permute(0, 2, 3, 1)                 # '(b t) h w c': the layout the stage writes
-                if tok.is_contiguous():
-                    hot_ops.place_output("swin0", tok.view(n // self.T, self.T, h, w, c))
-            elif mem.is_contiguous():
-                hot_ops.place_output("encoder_memory", mem)
-            return body()
-        finally:
-            hot_ops.place_output(tag, None)
 
     def _clone_text(self, tx):
         return {k: self._like(tx[k]) for k in self._TEXT}
@@ -425,15 +397,15 @@ class TwoStreamClipGraph(PipelinedClipGraph):
                 dst[k].copy_(tx[k])
 
     # -- driving -----------------------------------------------------------------------------------------
-    def stage_inputs(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None,
-                     attn: Optional[torch.Tensor] = None) -> None:
-        """As ClipGraph.stage_inputs, on the caller's stream -- which first waits until Video-Swin and the text encoder of the
-        previous clip have read the static inputs."""
+    def stage_inputs(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None, attn: Optional[torch.Tensor] = None,
+                     slot: int = 0) -> None:
+        """As the base's, on the caller's stream -- which first waits until Video-Swin and the text encoder of the previous clip
+        have read the static inputs."""
         if self._inputs_busy:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(self._ev_clip_free)
             cur.wait_event(self._ev_text)
-        ClipGraph.stage_inputs(self, clip, ids, attn)
+        super().stage_inputs(clip, ids, attn, slot)
 
     def replay(self):
         dev, k = self.device, self._n % 2
@@ -518,85 +490,8 @@ class PairPipelinedClipGraph(PipelinedClipGraph):
 
     CLIPS = 2
 
-    @_holds_what_it_captures
-    def __init__(self, model, T: int, H: int, W: int, L: int, device, warmup: int = 2):
-        self.model, self.T, self.H, self.W, self.L = model, T, H, W, L
-        dev = self.device = torch.device(device)
-        n = self.CLIPS
-        # stored clip-major: the backbone's '(b t)' flatten of the [T,B,...] samples is then a view, not an 88 MB copy per replay
-        import os
-        if os.environ.get("SOC_GROUP_SEQ_FIRST") == "1":
-            self.clip, self.pad = torch.zeros(T, n, 3, H, W, device=dev), torch.zeros(T, n, H, W, dtype=torch.bool, device=dev)
-        else:
-            self.clip = torch.zeros(n, T, 3, H, W, device=dev).transpose(0, 1)
-            self.pad = torch.zeros(n, T, H, W, dtype=torch.bool, device=dev).transpose(0, 1)
-        self.ids = torch.ones(n, L, dtype=torch.long, device=dev)
-        self.attn = torch.ones(n, L, dtype=torch.long, device=dev)
-        self.targets = [[{"size": (H, W)}] for _ in range(T)]              # of ONE clip: the tail runs per clip
-        hm, wm = -(-H // 4), -(-W // 4)
-        self.record = torch.zeros(n, CP.record_size(T, model.num_queries, hm, wm), device=dev)
-        self._finish_init(warmup)
-
-    def _finish_init(self, warmup):
-        """PipelinedClipGraph.__init__ behind the static buffers: warm-up, double-buffered state, the four captures."""
-        dev = self.device
-        assert not hot_ops.op_profile.active(), "do not capture while kernel profiling is on"
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(max(warmup, 1)):
-                sb = self._head(fork=False)
-                self._tail(sb, fork=False)
-            self.sb = [self._clone(sb), self._clone(sb)]
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        import os
-        self._pc = torch.cuda.Stream(device=dev, priority=0 if os.environ.get("SOC_TAIL_PRIORITY", "1") == "0" else -1)
-
-        def capture(body):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                body()
-            return g
-
-        def tail_beside_head(k):
-            cur = torch.cuda.current_stream(dev)
-            self._pc.wait_stream(cur)
-            with torch.cuda.stream(self._pc):
-                self._tail(self.sb[1 - k], fork=False)
-            self._store(self._placed_head(self.sb[k]), self.sb[k])
-            cur.wait_stream(self._pc)
-
-        self.steady = [capture(lambda k=k: tail_beside_head(k)) for k in (0, 1)]
-        self.drain = [capture(lambda k=k: self._tail(self.sb[k], fork=True)) for k in (0, 1)]
-        self.first = capture(lambda: self._store(self._placed_head(self.sb[0]), self.sb[0]))      # head only: see the parent
-        self._n = 0
-
-    def _tail(self, sb, fork: bool):
-        import os
-        prev, hot_ops.row_chain_fusion = hot_ops.row_chain_fusion, os.environ.get("SOC_TAIL_ROW_FUSION", "0") == "1"
-        if os.environ.get("SOC_TAIL_NO_FORK", "0") == "1":
-            fork = False
-        try:
-            group_tail(self.model, sb, self.targets, fork, self.record)
-        finally:
-            hot_ops.row_chain_fusion = prev
-
-    def stage_inputs(self, clip: torch.Tensor, ids: Optional[torch.Tensor] = None, attn: Optional[torch.Tensor] = None,
-                     slot: int = 0) -> None:
-        """Copy ONE clip [T,3,H,W] (+ its token ids [1,L] / [L]) into slot `slot` (0 .. CLIPS - 1) of the group, on the current
-        stream."""
-        self.clip[:, slot].copy_(clip.view(self.clip.shape[0], *self.clip.shape[2:]), non_blocking=True)
-        if ids is not None:
-            self.ids[slot].copy_(ids.view(-1), non_blocking=True)
-            masked = self.__dict__.setdefault("_attn_masked", set())       # slots whose static mask is not all ones
-            if attn is None:
-                if slot in masked:
-                    self.attn[slot].fill_(1)
-                    masked.discard(slot)
-            else:
-                self.attn[slot].copy_(attn.view(-1), non_blocking=True)
-                masked.add(slot)
+    def _tail_body(self, sb, fork: bool):
+        group_tail(self.model, sb, self.targets, fork, self.record)
 
     def run(self, clips, ids=None, attn=None):
         """clips: two [T,3,H,W] tensors; ids / attn: two [1,L] tensors each (or None)."""
@@ -638,7 +533,6 @@ def pipeline_class(name: Optional[str] = None):
     overrides) or "two-stream".  Same GPU time per clip within the box-to-box spread (tools/experiments/pipeline_ab.py in
     one process: 6.44-6.51 ms both; bench.py on one of three boxes: two-stream 0.2 ms slower); the two-stream form needs
     0.25 ms of host time per clip for its four single-branch launches where the one multi-branch launch blocks 1.2-4.8 ms."""
-    import os
     name = name or os.environ.get("SOC_PIPELINE", "one-graph")
     if name.startswith("group") and name[5:].isdigit():          # "group10": ten clips per launch group
         return group_pipeline_class(int(name[5:]))

@@ -20,7 +20,7 @@ import torch
 
 from . import clip_parallel as CP
 from . import postprocessing as P
-from .graph_runner import ClipGraph, PipelinedClipGraph, pipeline_class
+from .graph_runner import ClipGraph, PipelinedClipGraph, group_pipeline_class, pipeline_class
 from .nested_tensor import NestedTensor
 
 
@@ -115,14 +115,17 @@ class ClipInferencer:
         self._singles.clear()
         self._captured_under = self._weights_state()
 
-    def graph_for(self, T: int, H: int, W: int, L: int) -> ClipGraph:
-        key = (T, H, W, L)
-        if key not in self._graphs:
-            while len(self._graphs) >= self.max_graphs:      # a graph pins its activation pool: keep few
+    def _runner(self, held: Dict, key, runner_class):
+        """held[key], built as runner_class()(model, *key, device) on first use, behind the eviction of the oldest runners of `held`."""
+        if key not in held:
+            while len(held) >= self.max_graphs:              # a graph pins its activation pool: keep few
                 torch.cuda.synchronize(self.device)          # never drop a graph that may still be replaying
-                self._graphs.pop(next(iter(self._graphs)))
-            self._graphs[key] = ClipGraph(self.model, T, H, W, L, self.device)
-        return self._graphs[key]
+                held.pop(next(iter(held)))
+            held[key] = runner_class()(self.model, *key, self.device)
+        return held[key]
+
+    def graph_for(self, T: int, H: int, W: int, L: int) -> ClipGraph:
+        return self._runner(self._graphs, (T, H, W, L), lambda: ClipGraph)
 
     # -- streaming form: the software-pipelined graph (tail of clip i beside the head of clip i+1) ---------------
     def _pad_tokens(self, token_ids: torch.Tensor):
@@ -145,14 +148,16 @@ class ClipInferencer:
         return res
 
     def _pipeline(self, key):
-        if key not in self._pipes:
-            while len(self._pipes) >= self.max_graphs:
-                torch.cuda.synchronize(self.device)
-                self._pipes.pop(next(iter(self._pipes)))
-            from .graph_runner import group_pipeline_class
-            cls = pipeline_class() if self.group == 1 else group_pipeline_class(self.group)
-            self._pipes[key] = cls(self.model, *key, self.device)
-        return self._pipes[key]
+        return self._runner(self._pipes, key, lambda: pipeline_class() if self.group == 1 else group_pipeline_class(self.group))
+
+    def _single_pipeline(self, key):
+        return self._runner(self._singles, key, pipeline_class)
+
+    def _unpack_rows(self, rec: torch.Tensor, key, clips):
+        """rec: what a replay or a flush of this engine's pipeline hands out -- one record for group = 1, a row per slot
+        otherwise; clips: the (tag, original_size) of the slots that were filled."""
+        rows = rec if self.group > 1 else [rec]
+        return [self._unpack(rows[b], key, tag, osz) for b, (tag, osz) in enumerate(clips)]
 
     def _replay(self):
         """Replay the group that has been staged; -> result dicts of the group replayed one call earlier."""
@@ -167,8 +172,7 @@ class ClipInferencer:
         self._active = (key, pipe, filled)
         if rec is None or not in_flight:
             return []
-        rows = rec if self.group > 1 else [rec]
-        return [self._unpack(rows[b], key, tag, osz) for b, (tag, osz) in enumerate(in_flight)]
+        return self._unpack_rows(rec, key, in_flight)
 
     @torch.no_grad()
     def submit(self, clip: torch.Tensor, token_ids: torch.Tensor, tag, original_size=None):
@@ -190,22 +194,11 @@ class ClipInferencer:
         pipe = self._pipeline(key)
         if self._active is None:
             self._active = (key, pipe, [])
-        if self.group > 1:
-            pipe.stage_inputs(clip, ids, attn, slot=len(self._filling))
-        else:
-            pipe.stage_inputs(clip, ids, attn)
+        pipe.stage_inputs(clip, ids, attn, slot=len(self._filling))
         self._filling.append((tag, original_size))
         if len(self._filling) == self.group:
             out += self._replay()
         return out
-
-    def _single_pipeline(self, key):
-        if key not in self._singles:
-            while len(self._singles) >= self.max_graphs:
-                torch.cuda.synchronize(self.device)
-                self._singles.pop(next(iter(self._singles)))
-            self._singles[key] = pipeline_class()(self.model, *key, self.device)
-        return self._singles[key]
 
     def _remainder_through_singles(self):
         """A part-filled group of fewer than group / 2 clips: the group in flight is flushed, then the staged clips -- read back from
@@ -215,7 +208,7 @@ class ClipInferencer:
         key, pipe, in_flight = self._active
         out = []
         for rec in pipe.flush():
-            out += [self._unpack(rec[b], key, tag, osz) for b, (tag, osz) in enumerate(in_flight)]
+            out += self._unpack_rows(rec, key, in_flight)
         staged, self._filling = self._filling, []
         single = self._single_pipeline(key)
         for b, (tag, osz) in enumerate(staged):
@@ -243,8 +236,7 @@ class ClipInferencer:
         key, pipe, in_flight = self._active
         self._active = None
         for rec in pipe.flush():
-            rows = rec if self.group > 1 else [rec]
-            out += [self._unpack(rows[b], key, tag, osz) for b, (tag, osz) in enumerate(in_flight)]
+            out += self._unpack_rows(rec, key, in_flight)
         return out
 
     @torch.no_grad()
@@ -253,12 +245,7 @@ class ClipInferencer:
         T, _, H, W = clip.shape
         if self.use_graphs:
             self._check_weights()
-            ids, attn = token_ids.view(1, -1), None
-            L = ids.shape[-1]
-            if self.pad_tokens_to is not None and L < self.pad_tokens_to:
-                extra = self.pad_tokens_to - L
-                attn = torch.cat([torch.ones_like(ids), ids.new_zeros(1, extra)], 1)
-                ids = torch.cat([ids, ids.new_full((1, extra), self.PAD_ID)], 1)
+            ids, attn = self._pad_tokens(token_ids)
             g = self.graph_for(T, H, W, ids.shape[-1])
             return g.run(clip, ids, attn), g.record
         samples = NestedTensor(clip[:, None], torch.zeros(T, 1, H, W, dtype=torch.bool, device=clip.device),

@@ -333,7 +333,7 @@ class SOC(nn.Module):
         text_pos = sa["text_pos"]
         # A launch group (B > 1): '(t h w) b c' would be a real permute of every level (118 MB each way at level 0 for four
         # clips); the fusion is a cross-attention per clip, so it runs batch-first on the 'b (t h w) c' view of the tokens.
-        clip_major = B > 1 and device.type == "cuda" and os.environ.get("SOC_GROUP_SEQ_FIRST") != "1"
+        clip_major = B > 1 and device.type == "cuda"              # (the CPU keeps the reference's sequence-first layouts)
         if clip_major:
             words, text_pos = words.transpose(0, 1).contiguous(), text_pos.transpose(0, 1).contiguous()
         to_seq = self._seq_clip_major if clip_major else self._seq

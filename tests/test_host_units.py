@@ -276,3 +276,82 @@ def test_slice_state_gives_views_of_a_sub_group():
     assert torch.equal(singles[3]["ctx"][0], memory[3 * T:]) and torch.equal(singles[0]["lang_last"], state["lang_last"][:, :1])
     one = dict(state, B=1)
     assert SOC.split_state(one) == [one]
+
+
+@pytest.mark.parametrize("clips", [1, 3])
+def test_pipelined_runner_replay_order(clips):
+    """PipelinedClipGraph and a launch group drive their captured graphs alike: head only after a flush, then steady graphs 1, 0, 1 ...
+    (graph k fills sb[k]), and a flush drains the state the last head wrote.  No GPU: the graphs are stubs that log their name."""
+    from neurips2023_soc_amd import graph_runner as G
+    cls = G.PipelinedClipGraph if clips == 1 else G.group_pipeline_class(clips)
+    log = []
+
+    class Stub:
+        def __init__(self, name):
+            self.name = name
+
+        def replay(self):
+            log.append(self.name)
+
+    g = object.__new__(cls)
+    g.first, g.steady, g.drain = Stub("first"), [Stub("steady0"), Stub("steady1")], [Stub("drain0"), Stub("drain1")]
+    g._n, g.record = 0, torch.zeros(4) if clips == 1 else torch.zeros(clips, 4)
+    assert g.CLIPS == clips and g.DEPTH == 2
+    assert [g.replay() for _ in range(3)] == [None, g.record, g.record]
+    flushed = [g.flush()]
+    assert g.replay() is None
+    flushed += [g.flush(), g.flush()]
+    assert log == ["first", "steady1", "steady0", "drain0", "first", "drain0"]
+    assert [len(f) for f in flushed] == [1, 1, 0]
+    assert all(torch.equal(f[0], g.record) and f[0].data_ptr() != g.record.data_ptr() for f in flushed[:2])
+
+
+@pytest.mark.parametrize("clips", [1, 3])
+def test_runner_static_inputs_and_staging(clips, monkeypatch):
+    """The one allocation rule and the one stage_inputs of every graph runner, on CPU buffers: layouts per clip count, accepted
+    input shapes, and the attention mask of a slot going back to ones when ids are staged without one -- per slot."""
+    from neurips2023_soc_amd import graph_runner as G
+
+    class Model:
+        num_queries = 2
+
+    fills, fill_ = [], torch.Tensor.fill_
+    monkeypatch.setattr(torch.Tensor, "fill_", lambda t, v: fills.append(v) or fill_(t, v))
+    T, H, W, L = 2, 8, 8, 5
+    g = object.__new__(G.ClipGraph if clips == 1 else G.group_pipeline_class(clips))
+    g._allocate(Model(), T, H, W, L, "cpu")
+    R = g.record.shape[-1]
+    assert g.clip.shape == (T, clips, 3, H, W) and g.pad.shape == (T, clips, H, W) and g.pad.dtype == torch.bool
+    assert g.ids.shape == g.attn.shape == (clips, L) and len(g.targets) == T
+    flat = g.clip.transpose(0, 1).flatten(0, 1)                  # the backbone's '(b t)' flatten: a view for every clip count
+    assert flat.data_ptr() == g.clip.data_ptr() and flat.is_contiguous()
+    if clips == 1:
+        assert g.clip.is_contiguous() and g.record.dim() == 1 and g.record[None].shape == (1, R)
+    else:
+        assert g.record.shape == (clips, R)
+    ids, mask = torch.arange(2, 2 + L), torch.tensor([1, 1, 1, 0, 0])
+    clip = torch.randn(T, 3, H, W)
+    if clips == 1:
+        g.stage_inputs(clip, ids[None], mask[None])
+        assert torch.equal(g.clip[:, 0], clip) and torch.equal(g.ids[0], ids) and torch.equal(g.attn[0], mask)
+        g.stage_inputs(2 * clip[:, None], ids[None] + 1)          # [T,1,3,H,W]; no mask: ones again
+        assert torch.equal(g.clip[:, 0], 2 * clip) and torch.equal(g.ids[0], ids + 1) and bool((g.attn == 1).all())
+        g.stage_inputs(clip, ids[None], mask[None])
+        g.stage_inputs(3 * clip)                                  # ids=None: ids and mask stay as staged
+        assert torch.equal(g.clip[:, 0], 3 * clip) and torch.equal(g.ids[0], ids) and torch.equal(g.attn[0], mask)
+    else:
+        g.stage_inputs(clip, ids[None], mask[None], slot=1)       # ids as [1,L] ...
+        g.stage_inputs(2 * clip, ids + 1, mask.flip(0), slot=2)   # ... or [L]
+        assert torch.equal(g.clip[:, 1], clip) and torch.equal(g.clip[:, 2], 2 * clip) and not g.clip[:, 0].any()
+        assert torch.equal(g.attn[1], mask) and torch.equal(g.attn[2], mask.flip(0))
+        g.stage_inputs(3 * clip, ids + 2, slot=1)                 # slot 1 back to ones, slot 2 as staged
+        assert torch.equal(g.clip[:, 1], 3 * clip) and torch.equal(g.ids[1], ids + 2) and torch.equal(g.ids[2], ids + 1)
+        assert bool((g.attn[1] == 1).all()) and torch.equal(g.attn[2], mask.flip(0))
+        assert bool((g.ids[0] == 1).all()) and bool((g.attn[0] == 1).all())      # never staged
+    # staging adds no launch: the mask was refilled once above, for the slot that held another one, and an unmasked slot never is
+    assert len(fills) == 1
+    g.stage_inputs(clip, ids, mask, slot=clips - 1)
+    for _ in range(2):
+        g.stage_inputs(clip, ids, slot=clips - 1)
+        g.stage_inputs(clip, ids, slot=0)
+    assert len(fills) == 2

@@ -1,8 +1,9 @@
 """Do HIP stream priorities reach the branches of the pipelined graph?  (experiment, result in README.md: no)
 
-The capture-priority rows need this two-line patch of graph_runner.PipelinedClipGraph.__init__ (not in the tree):
+The capture-priority rows need this two-line patch of graph_runner.PipelinedClipGraph._build, the one place the tail's stream is
+made and the graphs are captured (not in the tree):
     self._pc = torch.cuda.Stream(device=dev, priority=self.TAIL_PRIORITY)
-    cap = torch.cuda.Stream(device=dev, priority=self.HEAD_PRIORITY);  with torch.cuda.graph(g, stream=cap): ...
+    cap = torch.cuda.Stream(device=dev, priority=self.HEAD_PRIORITY);  ... capture(body, stream=cap) for every graph
 Without it only the last row (launching the replays from a high-priority stream) measures anything."""
 import sys
 import time
