@@ -38,6 +38,16 @@ size_t soc_png_bound(int h, int w);
 long soc_png_encode_u8(const uint8_t* img, int h, int w, long row_stride, int binarize, const uint8_t* palette_rgb,
                        int n_colors, uint8_t* out, size_t cap);
 
+/*
+ * Bit-packed mask [h] rows of `row_stride` bytes (row_stride >= ceil(w / 8); pixel x of a row is bit x % 8 of byte x / 8,
+ * the format of soc_hip_bits.h) -> the SAME file, byte for byte, that soc_png_encode_u8(binarize = 1, palette_rgb = NULL)
+ * writes for the unpacked mask: same IHDR, same "Up"-filtered stream, same literal / run decisions, same checksums.  The
+ * filtered bytes are never materialised: runs are walked over 64-bit words of (row ^ row above) with count-trailing-zeros.
+ * Bits at positions >= w of a row are ignored (masked), whatever they hold.  `cap` >= soc_png_bound(h, w).
+ * Returns the number of bytes written, or -1 bad argument, -2 `cap` too small (-3 is never returned: nothing is allocated).
+ */
+long soc_png_encode_bits(const uint8_t* bits, int h, int w, long row_stride, uint8_t* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,9 @@
 // index / weight arithmetic restates torch's upsample_bilinear2d (scale = in / out,
 // src = max(scale * (dst + 0.5) - 0.5, 0), second tap clamped to the last row / column);
 // sigmoid(x) > 0.5 is evaluated as x > 0 (they differ only for 0 < x < 1.2e-7, where fp32
-// sigmoid rounds to exactly 0.5).
+// sigmoid rounds to exactly 0.5).  The per-pixel arithmetic lives in upsample_tap.h, shared with K6b (the bit-packed form).
 #include "soc_common.h"
+#include "upsample_tap.h"
 
 namespace {
 
@@ -22,23 +23,12 @@ __global__ __launch_bounds__(256) void upsample_threshold_kernel(
     const int y = blockIdx.y;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * PX;
     if (x0 >= W0) return;
-    const float fy = fmaxf(sy * ((float)y + 0.5f) - 0.5f, 0.f);
-    const int y1 = (int)fy;
-    const int yp = (y1 < h - 1) ? 1 : 0;
-    const float ly1 = fy - (float)y1, ly0 = 1.f - ly1;
-    const float* r0 = logits + ((long)t * h + y1) * w;
-    const float* r1 = r0 + (long)yp * w;
+    const soc_up_rows rows = soc_up_rows_of(logits + (long)t * h * w, y, h, w, sy);
     union { uint8_t b[PX]; uint4 v; } res;
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
         const int x = x0 + i;
-        const float fx = fmaxf(sx * ((float)x + 0.5f) - 0.5f, 0.f);
-        int x1 = (int)fx;
-        x1 = x1 < w - 1 ? x1 : w - 1;
-        const int xp = (x1 < w - 1) ? 1 : 0;
-        const float lx1 = fx - (float)x1, lx0 = 1.f - lx1;
-        const float v = ly0 * (lx0 * r0[x1] + lx1 * r0[x1 + xp]) + ly1 * (lx0 * r1[x1] + lx1 * r1[x1 + xp]);
-        res.b[i] = (x < W0 && v > thr) ? 1 : 0;
+        res.b[i] = (x < W0 && soc_up_pixel_above(rows, x, w, sx, thr)) ? 1 : 0;
     }
     uint8_t* o = out + ((long)t * H0 + y) * W0 + x0;
     if (x0 + PX <= W0 && (((uintptr_t)o) & 15) == 0) {

@@ -120,6 +120,65 @@ static uint8_t* chunk(uint8_t* p, const char type[4], const uint8_t* data, uint3
     return p + 12 + len;
 }
 
+/* one maximal run of `len` >= 1 bytes b of the filtered stream: a literal, then (run_rest) distance-1 matches of up to 258, then
+ * what is left (< 3) as literals -- the ONLY way either encoder below writes data, so equal filtered streams give equal files */
+static inline void run_rest(bitw* w, adler* ad, uint8_t b, size_t len) {
+    adler_run(ad, b, (uint64_t)len);
+    size_t run = len - 1;
+    while (run >= 3) {
+        const int n = run >= 258 ? 258 : (int)run;
+        put_run(w, n);
+        run -= (size_t)n;
+    }
+    while (run--) put_literal(w, b);
+}
+
+static inline void emit_run(bitw* w, adler* ad, uint8_t b, size_t len) {
+    put_literal(w, b);
+    run_rest(w, ad, b, len);
+}
+
+/* signature, IHDR, optional PLTE; returns where the IDAT chunk starts */
+static uint8_t* png_head(uint8_t* p, int h, int w, const uint8_t* palette_rgb, int n_colors) {
+    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    memcpy(p, sig, 8);
+    p += 8;
+    uint8_t ihdr[13];
+    put_u32be(ihdr, (uint32_t)w);
+    put_u32be(ihdr + 4, (uint32_t)h);
+    ihdr[8] = 8;
+    ihdr[9] = palette_rgb ? 3 : 0;
+    ihdr[10] = ihdr[11] = ihdr[12] = 0;
+    p = chunk(p, "IHDR", ihdr, 13);
+    if (palette_rgb) p = chunk(p, "PLTE", palette_rgb, (uint32_t)(3 * n_colors));
+    return p;
+}
+
+/* IDAT: zlib header, one final fixed-Huffman block (opened here), adler32.  idat_begin / idat_end are forced inline: a bit writer
+ * whose address leaves the encoder's frame is kept in memory, and every bw_put of the hot loop pays for it (about 5 % of an encode) */
+static inline __attribute__((always_inline)) bitw idat_begin(uint8_t* p, uint8_t* out, size_t cap) {
+    uint8_t* idat = p + 8;
+    bitw bw = {idat + 2, out + cap - 16, 0, 0, 0};
+    idat[0] = 0x78;
+    idat[1] = 0x01;
+    bw_put(&bw, 1, 1);                                /* BFINAL */
+    bw_put(&bw, 1, 2);                                /* BTYPE = 01 */
+    return bw;
+}
+
+/* end of block, adler32, the IDAT chunk around what was written behind p + 8, IEND; returns the file's length or -2 */
+static inline __attribute__((always_inline)) long idat_end(bitw* bw, const adler* ad, uint8_t* p, uint8_t* out, size_t cap) {
+    uint8_t* idat = p + 8;
+    bw_put(bw, lit_code[256], lit_bits[256]);         /* end of block */
+    if (bw->n) bw_put(bw, 0, 8 - bw->n);              /* flush to a byte boundary */
+    if (bw->overflow || bw->p + 4 > out + cap - 16) return -2;
+    put_u32be(bw->p, (uint32_t)((ad->b << 16) | ad->a));
+    const uint32_t idat_len = (uint32_t)(bw->p + 4 - idat);
+    p = chunk(p, "IDAT", idat, idat_len);
+    p = chunk(p, "IEND", NULL, 0);
+    return (long)(p - out);
+}
+
 long soc_png_encode_u8(const uint8_t* img, int h, int w, long row_stride, int binarize, const uint8_t* palette_rgb,
                        int n_colors, uint8_t* out, size_t cap) {
     if (!img || !out || h <= 0 || w <= 0 || row_stride < w) return -1;
@@ -145,26 +204,8 @@ long soc_png_encode_u8(const uint8_t* img, int h, int w, long row_stride, int bi
     }
     memset(raw + raw_n, 0xA5, 8);                     /* guard bytes for the 8-byte run scan (never equal to a run of zeros) */
 
-    uint8_t* p = out;
-    static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-    memcpy(p, sig, 8);
-    p += 8;
-    uint8_t ihdr[13];
-    put_u32be(ihdr, (uint32_t)w);
-    put_u32be(ihdr + 4, (uint32_t)h);
-    ihdr[8] = 8;
-    ihdr[9] = palette_rgb ? 3 : 0;
-    ihdr[10] = ihdr[11] = ihdr[12] = 0;
-    p = chunk(p, "IHDR", ihdr, 13);
-    if (palette_rgb) p = chunk(p, "PLTE", palette_rgb, (uint32_t)(3 * n_colors));
-
-    /* IDAT: zlib header, one final fixed-Huffman block, adler32 */
-    uint8_t* idat = p + 8;
-    bitw bw = {idat + 2, out + cap - 16, 0, 0, 0};
-    idat[0] = 0x78;
-    idat[1] = 0x01;
-    bw_put(&bw, 1, 1);                                /* BFINAL */
-    bw_put(&bw, 1, 2);                                /* BTYPE = 01 */
+    uint8_t* p = png_head(out, h, w, palette_rgb, n_colors);
+    bitw bw = idat_begin(p, out, cap);
     size_t i = 0;
     adler ad = {1, 0};
     while (i < raw_n) {
@@ -179,23 +220,71 @@ long soc_png_encode_u8(const uint8_t* img, int h, int w, long row_stride, int bi
             if (j + 8 <= raw_n && v == pat) j += 8; else break;
         }
         while (j < raw_n && raw[j] == b) ++j;
-        size_t run = j - i - 1;
-        adler_run(&ad, b, (uint64_t)(j - i));
-        while (run >= 3) {
-            const int len = run >= 258 ? 258 : (int)run;
-            put_run(&bw, len);
-            run -= (size_t)len;
-        }
-        while (run--) put_literal(&bw, b);
+        run_rest(&bw, &ad, b, j - i);
         i = j;
     }
-    bw_put(&bw, lit_code[256], lit_bits[256]);        /* end of block */
-    if (bw.n) bw_put(&bw, 0, 8 - bw.n);               /* flush to a byte boundary */
     free(raw);
-    if (bw.overflow || bw.p + 4 > out + cap - 16) return -2;
-    put_u32be(bw.p, (uint32_t)((ad.b << 16) | ad.a));
-    const uint32_t idat_len = (uint32_t)(bw.p + 4 - idat);
-    p = chunk(p, "IDAT", idat, idat_len);
-    p = chunk(p, "IEND", NULL, 0);
-    return (long)(p - out);
+    return idat_end(&bw, &ad, p, out, cap);
+}
+
+/* ---- the same file from a bit-packed mask (include/soc_hip_bits.h) ----------------------------------------------------
+ * Word k of a row holds pixels 64 k .. 64 k + 63, pixel x in bit x % 64 (bytes in memory order = little bit order).  With
+ * c = this row's word and p = the word of the row above, a filtered byte ("Up" of 0 / 255 pixels) is
+ *     0 where c ^ p is 0,   255 where c & ~p (a rise),   1 where ~c & p (a fall: 0 - 255 mod 256),
+ * so a run of equal filtered bytes ends at the next set bit of (c ^ p), ~(c & ~p) or ~(~c & p): one count-trailing-zeros per
+ * run, one pair of word loads per 64 pixels, and no filtered image in memory. */
+static inline uint64_t load_word(const uint8_t* row, size_t k, size_t nbytes, int w) {
+    uint64_t v;
+    const size_t at = 8 * k;
+    if (at + 8 <= nbytes) {
+        memcpy(&v, row + at, 8);                       /* (a fixed size: one load) */
+    } else {
+        v = 0;
+        memcpy(&v, row + at, nbytes - at);             /* the last word never reads past ceil(w / 8) bytes of the row */
+    }
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_BIG_ENDIAN__
+    v = __builtin_bswap64(v);
+#endif
+    const size_t left = (size_t)w - 64 * k;           /* pixels from this word on: bits at positions >= w are dropped */
+    return left < 64 ? v & (((uint64_t)1 << left) - 1) : v;
+}
+
+long soc_png_encode_bits(const uint8_t* bits, int h, int w, long row_stride, uint8_t* out, size_t cap) {
+    if (!bits || !out || h <= 0 || w <= 0) return -1;
+    const size_t nbytes = ((size_t)w + 7) / 8, words = ((size_t)w + 63) / 64;
+    if (row_stride < (long)nbytes) return -1;
+    if (cap < soc_png_bound(h, w)) return -2;
+    if (!huff_ready) huff_init();
+    uint8_t* p = png_head(out, h, w, NULL, 0);
+    bitw bw = idat_begin(p, out, cap);
+    adler ad = {1, 0};
+    for (int y = 0; y < h; ++y) {
+        const uint8_t* cur = bits + (size_t)y * (size_t)row_stride;
+        const uint8_t* up = y ? cur - row_stride : NULL;
+        emit_run(&bw, &ad, 2, 1);                     /* the filter type: never equal to a neighbour (0, 1 or 255) */
+        size_t x = 0, k = 0;
+        uint64_t c = load_word(cur, 0, nbytes, w), q = up ? load_word(up, 0, nbytes, w) : 0;
+        while (x < (size_t)w) {
+            const unsigned o = (unsigned)(x & 63);
+            const uint64_t d = c ^ q;
+            int kind;                                 /* 0: equal to the row above, 1: rise, 2: fall */
+            uint64_t m;                               /* set bits: where the run is over */
+            if (!((d >> o) & 1)) { kind = 0; m = d; }
+            else if ((c >> o) & 1) { kind = 1; m = ~(c & ~q); }
+            else { kind = 2; m = ~(~c & q); }
+            m &= ~(uint64_t)0 << o;
+            size_t end;
+            for (;;) {
+                if (m) { end = 64 * k + (size_t)__builtin_ctzll(m); break; }
+                if (++k >= words) { end = (size_t)w; break; }
+                c = load_word(cur, k, nbytes, w);
+                q = up ? load_word(up, k, nbytes, w) : 0;
+                m = kind == 0 ? c ^ q : kind == 1 ? ~(c & ~q) : ~(~c & q);
+            }
+            if (end > (size_t)w) end = (size_t)w;     /* (the complements have ones in the dropped bits of the last word) */
+            emit_run(&bw, &ad, kind == 0 ? 0 : kind == 1 ? 255 : 1, end - x);
+            x = end;
+        }
+    }
+    return idat_end(&bw, &ad, p, out, cap);
 }

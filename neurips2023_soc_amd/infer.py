@@ -62,8 +62,10 @@ class ClipInferencer:
     PAD_ID = 1            # RoBERTa <pad>
 
     def __init__(self, model, device="cuda", use_graphs: bool = True, max_graphs: int = 4,
-                 pad_tokens_to: Optional[int] = None, group: int = 1):
-        """pad_tokens_to: with graphs, pad every expression to this many tokens (<pad> + attention mask 0), so
+                 pad_tokens_to: Optional[int] = None, group: int = 1, packed_masks: bool = False):
+        """packed_masks: results carry 'masks_packed' (uint8 [T,H0,RB], one bit per pixel: packed_masks.py) and 'mask_size'
+        (H0, W0) instead of 'masks'; a group whose clips share one original size is up-sampled in ONE launch from the record.
+        pad_tokens_to: with graphs, pad every expression to this many tokens (<pad> + attention mask 0), so
         that the graph geometry does not depend on the expression.  The reference's outputs are exactly
         invariant to such padding (checked on the reference itself; tests/test_host_plumbing.py checks the
         oracle), which is what tokenizer(..., padding="longest") does to the shorter expressions of a batch."""
@@ -77,6 +79,7 @@ class ClipInferencer:
         if int(group) != group or group < 1:
             raise ValueError("group must be a positive clip count")
         self.group = group
+        self.packed_masks = bool(packed_masks)
         self._filling = []           # (tag, original_size) of the clips staged into the group that has not been replayed yet
         self._graphs: Dict[Tuple[int, int, int, int], ClipGraph] = {}
         self._pipes: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}
@@ -137,14 +140,22 @@ class ClipInferencer:
             ids = torch.cat([ids, ids.new_full((1, extra), self.PAD_ID)], 1)
         return ids, attn
 
-    def _unpack(self, rec: torch.Tensor, key, tag, original_size):
+    def _masks_into(self, res: Dict, masks: torch.Tensor, original_size, packed: Optional[torch.Tensor] = None):
+        """The full-size masks of one clip, in the form this engine was built for; `packed`: already up-sampled with its group."""
+        if not self.packed_masks:
+            res["masks"] = P.upsample_and_threshold(masks, original_size)
+        else:
+            res["masks_packed"] = P.upsample_and_threshold_packed(masks, original_size) if packed is None else packed
+            res["mask_size"] = (int(original_size[0]), int(original_size[1]))
+
+    def _unpack(self, rec: torch.Tensor, key, tag, original_size, packed: Optional[torch.Tensor] = None):
         T, H, W, _ = key
         Q = self.model.num_queries
         hm, wm = -(-H // 4), -(-W // 4)
         masks = rec[1 + T * Q:].view(T, hm, wm)
         res = {"tag": tag, "query": rec[0].to(torch.int64), "mask_logits": masks, "pred_cls": rec[1:1 + T * Q].view(T, Q)}
         if original_size is not None:
-            res["masks"] = P.upsample_and_threshold(masks, original_size)
+            self._masks_into(res, masks, original_size, packed)
         return res
 
     def _pipeline(self, key):
@@ -157,7 +168,18 @@ class ClipInferencer:
         """rec: what a replay or a flush of this engine's pipeline hands out -- one record for group = 1, a row per slot
         otherwise; clips: the (tag, original_size) of the slots that were filled."""
         rows = rec if self.group > 1 else [rec]
-        return [self._unpack(rows[b], key, tag, osz) for b, (tag, osz) in enumerate(clips)]
+        packed = None
+        sizes = {None if osz is None else (int(osz[0]), int(osz[1])) for _, osz in clips}
+        if self.packed_masks and self.group > 1 and len(clips) > 1 and len(sizes) == 1 and None not in sizes \
+                and rec.dim() == 2 and rec.stride(1) == 1:
+            # one original size in the group: K6b reads every filled row's mask logits where the record holds them
+            from . import packed_masks as PM
+            T, H, W, _ = key
+            first = rec[0, 1 + T * self.model.num_queries:].view(T, -(-H // 4), -(-W // 4))
+            packed = PM.upsample_threshold_bits(first, sizes.pop(), clip_stride=rec.stride(0), clips=len(clips))
+        if packed is None:
+            return [self._unpack(rows[b], key, tag, osz) for b, (tag, osz) in enumerate(clips)]
+        return [self._unpack(rows[b], key, tag, osz, packed=packed[b]) for b, (tag, osz) in enumerate(clips)]
 
     def _replay(self):
         """Replay the group that has been staged; -> result dicts of the group replayed one call earlier."""
@@ -180,7 +202,8 @@ class ClipInferencer:
         available -- those of the group of clips replayed one replay earlier (group = 1: the clip submitted before this one),
         preceded by whatever a geometry change had to drain; often empty.  Every result carries the `tag` / `original_size`
         given at its own submit.  Results: 'tag', 'query', 'mask_logits' (a view of the graph's record: consume it, e.g.
-        through 'masks', before the next submit), 'pred_cls', 'masks' when original_size was given.  `clip` may be reused by
+        through 'masks', before the next submit), 'pred_cls', 'masks' when original_size was given ('masks_packed' and
+        'mask_size' instead with packed_masks=True).  `clip` may be reused by
         the caller as soon as submit returns (it has been copied into the graph's static input)."""
         if not self.use_graphs:
             raise RuntimeError("submit() streams through hipGraphs; construct with use_graphs=True")
@@ -260,12 +283,13 @@ class ClipInferencer:
                  original_size: Optional[Sequence[int]] = None):
         """clip [T,3,H,W] (normalised, on the device), token_ids [1,L] -> dict with
         'query' (0-d int64 tensor), 'mask_logits' [T,H/4,W/4], 'pred_cls' [T,Q], and, when
-        original_size=(H0,W0) is given, 'masks' bool [T,H0,W0]."""
+        original_size=(H0,W0) is given, 'masks' bool [T,H0,W0] (packed_masks=True: 'masks_packed' uint8 [T,H0,RB] and
+        'mask_size' instead)."""
         out, record = self.forward_clip(clip, token_ids)
         idx, masks = P.select_trajectory(out)
         res = {"query": idx, "mask_logits": masks, "pred_cls": out["pred_cls"][:, 0, :, 0], "record": record}
         if original_size is not None:
-            res["masks"] = P.upsample_and_threshold(masks, original_size)
+            self._masks_into(res, masks, original_size)
         return res
 
 
@@ -338,12 +362,13 @@ def _run_dataset(a):
         tokenize = synthetic_dataset.HashTokenizer()
     driver = infer_refytb if a.dataset == "refytb" else infer_davis
     model = model.to(dev).eval()
-    engine = ClipInferencer(model, dev, use_graphs=a.graphs, pad_tokens_to=32, group=a.group if a.graphs else 1)   # shared across passes
-    extra = {}
+    engine = ClipInferencer(model, dev, use_graphs=a.graphs, pad_tokens_to=32, group=a.group if a.graphs else 1,
+                            packed_masks=a.packed_masks)   # shared across passes
+    extra = {"packed_masks": True} if a.packed_masks else {}
     if a.eval_davis:
         if a.dataset != "davis":
             raise RuntimeError("--eval-davis scores the output of --dataset davis")
-        extra = {"eval_root": a.eval_davis, "eval_task": a.eval_task}
+        extra.update(eval_root=a.eval_davis, eval_task=a.eval_task)
     for _ in range(max(a.repeat, 1)):
         stats = driver.run(model, tokenize, a.root, a.out, rank, world, dev, engine=engine, **extra)
     stats["clips_per_s"] = stats["expressions"] / stats["seconds"]
@@ -381,12 +406,17 @@ def parse_args(argv=None):
                          "ground truth is written to DIR first")
     ap.add_argument("--eval-task", default="unsupervised", choices=["semi-supervised", "unsupervised"],
                     help="--eval-davis: the DAVIS task (the reference's eval_davis.py default: unsupervised)")
+    ap.add_argument("--packed-masks", action="store_true",
+                    help="--dataset refytb: masks leave the GPU bit-packed (one bit per pixel, packed_masks.py) and the PNG files are "
+                         "encoded from the bits; same files as without the flag")
     ap.add_argument("--words", type=int, default=0, help="--make-synthetic: fixed number of words per expression")
     ap.add_argument("--repeat", type=int, default=1, help="run the driver this many times, report the last (warm) pass")
     ap.add_argument("--gpus", "-ng", type=int, default=None,
                     help="GPUs of this node; >1 without an outer launcher starts one rank per GPU (reference -ng).  "
                          "Default: WORLD_SIZE under an outer launcher, 1 otherwise; an explicit value must equal WORLD_SIZE")
     a = ap.parse_args(argv)
+    if a.packed_masks and a.dataset != "refytb":
+        ap.error("--packed-masks applies to --dataset refytb (the DAVIS driver writes label maps, which are not one-bit data)")
     if a.group is None:
         a.group = 8 if a.graphs else 1
     a.gpus_given = a.gpus is not None

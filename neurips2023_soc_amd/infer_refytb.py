@@ -48,6 +48,17 @@ def save_binary_mask(mask: np.ndarray, path: str) -> None:
         png_fast.save(path, mask, binarize=True)
 
 
+def save_packed_mask(bits: np.ndarray, width: int, path: str) -> None:
+    """save_binary_mask for a bit-packed mask [H, RB] of `width` pixels (packed_masks.py): the same file, byte for byte,
+    encoded straight from the bits (png_fast.encode_bits); with the Pillow writer the mask is unpacked first."""
+    from . import png_fast
+    if png_fast.use_pillow():
+        from . import packed_masks
+        save_binary_mask(packed_masks.unpack(bits, width), path)
+    else:
+        png_fast.save_bits(path, bits, width)
+
+
 def load_meta(root: str, split: str = "valid"):
     img_folder = os.path.join(root, split, "JPEGImages")
     with open(os.path.join(root, "meta_expressions", split, "meta_expressions.json")) as f:
@@ -61,13 +72,19 @@ PREFETCH_VIDEOS = 4          # videos decoded ahead of the one on the GPU (a 720
 def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world: int = 1, device="cuda",
         split: str = "valid", size: int = 360, max_size: Optional[int] = 640, use_graphs: bool = False,
         decode_workers: int = 8, writer_workers: int = 16, videos: Optional[Sequence[str]] = None,
-        engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1) -> Dict:
-    """Process this rank's videos; returns counters + timings.  group > 1 (with use_graphs): consecutive clips of one
+        engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1,
+        packed_masks: bool = False) -> Dict:
+    """Process this rank's videos; returns counters + timings.  packed_masks: the masks leave the GPU one bit per pixel (K6b, once
+    per group of one original size), the pinned buffers and the host copy are [T,H0,RB] uint8 -- an eighth -- and the writers encode
+    the PNGs from the bits; the files are the same.  group > 1 (with use_graphs): consecutive clips of one
     geometry share every launch of the forward, each still getting its single-clip result (ClipInferencer(group=...)).  `tokenize(expression) -> int64 [1,L]`
     (RobertaTokenizerFast in production; no vocabulary files exist offline, so the caller supplies it)."""
     img_folder, data = load_meta(root, split)
     todo = split_videos(sorted(data.keys()) if videos is None else list(videos), rank, world)
-    engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group)
+    engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group,
+                                      packed_masks=packed_masks)
+    if bool(getattr(engine, "packed_masks", False)) != bool(packed_masks):
+        raise ValueError("packed_masks of run() and of the engine it was given disagree")
     cache = clip_io.VideoClipCache(clip_io.FramePreprocessor(device, size, max_size), workers=decode_workers)
     stats = {"videos": 0, "expressions": 0, "frames": 0, "seconds_input": 0.0, "seconds_model": 0.0}
     pending = []
@@ -76,18 +93,22 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
     def flush(job):
         """clip i's masks -> PNG jobs; called after clip i+1 has been enqueued, so the D2H copy, the numpy
         view and the job submission overlap the next forward instead of idling the GPU"""
-        host, done, save_dir, names = job
+        host, done, save_dir, names, width = job
         done.synchronize()
-        masks = host.numpy().copy()            # the pinned buffer is reused two clips later
+        masks = host.numpy().copy()            # the pinned buffer is reused two clips later (packed: an eighth of the bytes)
         for j, name in enumerate(names):
-            pending.append(writers.submit(save_binary_mask, masks[j], os.path.join(save_dir, name + ".png")))
+            path = os.path.join(save_dir, name + ".png")
+            if width is None:
+                pending.append(writers.submit(save_binary_mask, masks[j], path))
+            else:
+                pending.append(writers.submit(save_packed_mask, masks[j], width, path))
 
     pinned: Dict = {}                      # two host buffers per mask shape, reused (pinning is slow)
 
-    def host_buffer(shape, slot):
-        key = (tuple(shape), slot)
+    def host_buffer(shape, slot, dtype):
+        key = (tuple(shape), slot, dtype)
         if key not in pinned:
-            pinned[key] = torch.empty(tuple(shape), dtype=torch.bool, pin_memory=True)
+            pinned[key] = torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
         return pinned[key]
 
     d2h = torch.cuda.Stream(device=device)    # mask download overlaps the next clip's forward
@@ -100,8 +121,9 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
 
     def enqueue_download(res):
         """masks of a finished clip -> pinned host buffer on the d2h stream; returns the job for flush()"""
-        masks, (save_dir, names) = res["masks"], res["tag"]
-        host = host_buffer(masks.shape, enqueue_download.n % (2 * lag + 2))
+        save_dir, names = res["tag"]
+        masks, width = (res["masks_packed"], res["mask_size"][1]) if packed_masks else (res["masks"], None)
+        host = host_buffer(masks.shape, enqueue_download.n % (2 * lag + 2), masks.dtype)
         enqueue_download.n += 1
         d2h.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(d2h):
@@ -109,7 +131,7 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
             masks.record_stream(d2h)
             done = torch.cuda.Event()
             done.record()
-        return (host, done, save_dir, names)
+        return (host, done, save_dir, names, width)
     enqueue_download.n = 0
 
     import collections

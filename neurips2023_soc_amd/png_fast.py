@@ -20,7 +20,7 @@ ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libsoc_host.so")
 SOURCES = [os.path.join(_PKG, "csrc_host", "png_runs.c")]
 HEADER = os.path.join(ROOT, "include", "soc_host.h")
-EXPORTS = ("soc_host_abi_version", "soc_png_bound", "soc_png_encode_u8")
+EXPORTS = ("soc_host_abi_version", "soc_png_bound", "soc_png_encode_u8", "soc_png_encode_bits")
 ABI_VERSION = 1
 
 _lib = None
@@ -69,6 +69,8 @@ def load() -> C.CDLL:
             lib.soc_png_encode_u8.restype = C.c_long
             lib.soc_png_encode_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_size_t]
+            lib.soc_png_encode_bits.restype = C.c_long
+            lib.soc_png_encode_bits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_size_t]
             if lib.soc_host_abi_version() != ABI_VERSION:
                 raise RuntimeError("libsoc_host.so ABI version mismatch; rebuild it")
             _lib = lib
@@ -90,10 +92,7 @@ def encode(img: np.ndarray, binarize: bool = False, palette: Optional[Sequence[i
     if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
         a = np.ascontiguousarray(a)
     h, w = a.shape
-    cap = lib.soc_png_bound(h, w)
-    buf = getattr(_scratch, "buf", None)
-    if buf is None or buf.size < cap:
-        buf = _scratch.buf = np.empty(cap, np.uint8)
+    buf = _scratch_buffer(lib.soc_png_bound(h, w))
     pal_ptr, n_colors = None, 0
     if palette is not None:
         pal = np.asarray(list(palette), dtype=np.uint8)
@@ -105,6 +104,31 @@ def encode(img: np.ndarray, binarize: bool = False, palette: Optional[Sequence[i
     n = lib.soc_png_encode_u8(a.ctypes.data, h, w, a.strides[0], int(bool(binarize)), pal_ptr, n_colors, buf.ctypes.data, buf.size)
     if n <= 0:
         raise RuntimeError(f"soc_png_encode_u8 failed ({n})")
+    return buf[:n].tobytes()
+
+
+def _scratch_buffer(cap: int) -> np.ndarray:
+    buf = getattr(_scratch, "buf", None)
+    if buf is None or buf.size < cap:
+        buf = _scratch.buf = np.empty(cap, np.uint8)
+    return buf
+
+
+def encode_bits(bits: np.ndarray, w: int) -> bytes:
+    """[H, RB] uint8 bit-packed mask of width `w` (packed_masks: pixel x = bit x % 8 of byte x // 8; any row stride >= ceil(w / 8),
+    contiguous along the row) -> the bytes encode(mask, binarize=True) returns for the unpacked mask, without unpacking it."""
+    lib = load()
+    a = np.asarray(bits)
+    w = int(w)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] < 1 or w < 1 or a.shape[1] * 8 < w:
+        raise ValueError(f"encode_bits: expected a non-empty [H, >= ceil(w / 8)] uint8 array, got {a.dtype} {a.shape} for w = {w}")
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    h = a.shape[0]
+    buf = _scratch_buffer(lib.soc_png_bound(h, w))
+    n = lib.soc_png_encode_bits(a.ctypes.data, h, w, a.strides[0], buf.ctypes.data, buf.size)
+    if n <= 0:
+        raise RuntimeError(f"soc_png_encode_bits failed ({n})")
     return buf[:n].tobytes()
 
 
@@ -137,5 +161,11 @@ def pillow_save_kwargs() -> dict:
 
 def save(path: str, img: np.ndarray, binarize: bool = False, palette: Optional[Sequence[int]] = None) -> None:
     data = encode(img, binarize, palette)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def save_bits(path: str, bits: np.ndarray, w: int) -> None:
+    data = encode_bits(bits, w)
     with open(path, "wb") as f:
         f.write(data)

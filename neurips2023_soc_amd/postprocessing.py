@@ -31,6 +31,16 @@ def upsample_and_threshold(mask_logits: torch.Tensor, size: Sequence[int]) -> to
     return up.sigmoid() > 0.5
 
 
+def upsample_and_threshold_packed(mask_logits: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
+    """upsample_and_threshold with one BIT per pixel: [T,h,w] logits -> uint8 [T,H0,RB], the packed format of packed_masks.py
+    (row_bytes(W0) bytes per row, pixel x = bit x % 8 of byte x // 8).  On the GPU the fused HIP kernel K6b; CPU tensors take
+    the reference's two torch ops and pack()."""
+    from . import packed_masks
+    if mask_logits.is_cuda:
+        return packed_masks.upsample_threshold_bits(mask_logits, size)
+    return packed_masks.pack(upsample_and_threshold(mask_logits, size))
+
+
 def merge_davis_objects(soft_masks: torch.Tensor, threshold: float = 0.5, background: float = 0.1) -> torch.Tensor:
     """soft_masks [O,T,H,W] sigmoid scores of O objects -> label map [T,H,W] (0 = background)."""
     m = torch.where(soft_masks < threshold, torch.zeros_like(soft_masks), soft_masks)

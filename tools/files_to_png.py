@@ -20,6 +20,7 @@ ap.add_argument("--videos", type=int, default=64)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "r05_files_to_png.json"))
 ap.add_argument("--group", type=int, default=8, help="clips per launch group of the driver's graph pipeline (the driver's default with --graphs: 8)")
 ap.add_argument("--ragged", action="store_true", help="1-5 expressions per video (as the real set: infer_refytb.py:185), mean 3, instead of 3 each")
+ap.add_argument("--packed-masks", action="store_true", help="passed through to the driver: bit-packed masks from the kernel to the PNG encoder")
 a = ap.parse_args()
 
 import numpy as np  # noqa: E402
@@ -33,7 +34,7 @@ counts = [(1, 3, 5, 2, 4, 3, 2, 4)[v % 8] for v in range(a.videos)] if a.ragged 
 synthetic_dataset.make_dataset(root, videos=a.videos, frames=8, expressions=counts, n_words=8)
 # ---- the driver itself, warm pass reported (child process: its own GPU context, the parent stays CPU-only)
 cmd = [sys.executable, "-m", "neurips2023_soc_amd.infer", "--dataset", "refytb", "--root", root, "--out", out_dir, "--graphs",
-       "--repeat", "2", "--group", str(a.group)]
+       "--repeat", "2", "--group", str(a.group)] + (["--packed-masks"] if a.packed_masks else [])
 t0 = time.perf_counter()
 r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
 wall = time.perf_counter() - t0
