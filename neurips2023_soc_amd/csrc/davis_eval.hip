@@ -19,7 +19,15 @@
 //                                                       `radius` halo rows and one halo word per side in LDS (<= 43.5 KB at
 //                                                       radius 64); rows / words outside the image are zero there
 //   counts    AND / OR + popcount over planes           one workgroup per (pair, frame), written straight into `counts`
+//
+// K27b (soc_hip_jf_bits.h), the per-expression form: E predictions that are ALREADY bit planes in this layout (K6b's output,
+// packed_masks.py) against O distinct ground-truth objects, expression e against object exp_obj[e].  Per frame there are
+// NP = O + E planes (objects, then expressions); the planes kernel builds the O object planes from the label maps with
+// ballots, as above, and the E prediction planes by one 64-bit load per word, ANDed with the wave's "inside the image and
+// not void" ballot -- the predictions are never expanded to bytes, and their padding bits never reach a plane.  Boundary
+// and dilation are the kernels above, run once per plane: an object's three planes serve every expression that names it.
 #include "soc_common.h"
+#include "soc_hip_jf_bits.h"
 
 namespace {
 
@@ -137,20 +145,11 @@ __global__ __launch_bounds__(256) void dilate_kernel(const u64* __restrict__ bnd
     }
 }
 
-// One workgroup per (row of `counts`, frame of the chunk).  pairs: row = i * P + j; otherwise row = k (object k against
-// prediction k, an empty mask for k >= P).
-__global__ __launch_bounds__(256) void counts_kernel(const u64* __restrict__ mask, const u64* __restrict__ bnd,
-                                                     const u64* __restrict__ dil, int32_t* __restrict__ counts, int G, int P,
-                                                     int T, int t0, int Tc, long plane_words, int pairs) {
+// The six counts of ground-truth plane `gi` against prediction plane `pj` (word offsets of the planes; no prediction: an
+// empty mask), summed by the whole workgroup and written to out[0..5].
+__device__ inline void count_planes(const u64* __restrict__ mask, const u64* __restrict__ bnd, const u64* __restrict__ dil,
+                                    long gi, long pj, bool have_pred, long plane_words, int32_t* __restrict__ out) {
     __shared__ int acc[6];
-    const int tl = blockIdx.x % Tc;
-    const int row = blockIdx.x / Tc;
-    const int i = pairs ? row / P : row;
-    const int j = pairs ? row % P : row;
-    const bool have_pred = j < P;
-    const int NP = G + P;
-    const long gi = ((long)tl * NP + i) * plane_words;
-    const long pj = ((long)tl * NP + G + (have_pred ? j : 0)) * plane_words;
     if (threadIdx.x < 6) acc[threadIdx.x] = 0;
     __syncthreads();
     int c[6] = {0, 0, 0, 0, 0, 0};
@@ -171,7 +170,77 @@ __global__ __launch_bounds__(256) void counts_kernel(const u64* __restrict__ mas
         if ((threadIdx.x & 63) == 0) atomicAdd(&acc[q], v);            // integer: the order does not matter
     }
     __syncthreads();
-    if (threadIdx.x < 6) counts[((long)row * T + t0 + tl) * 6 + threadIdx.x] = acc[threadIdx.x];
+    if (threadIdx.x < 6) out[threadIdx.x] = acc[threadIdx.x];
+}
+
+// One workgroup per (row of `counts`, frame of the chunk).  pairs: row = i * P + j; otherwise row = k (object k against
+// prediction k, an empty mask for k >= P).
+__global__ __launch_bounds__(256) void counts_kernel(const u64* __restrict__ mask, const u64* __restrict__ bnd,
+                                                     const u64* __restrict__ dil, int32_t* __restrict__ counts, int G, int P,
+                                                     int T, int t0, int Tc, long plane_words, int pairs) {
+    const int tl = blockIdx.x % Tc;
+    const int row = blockIdx.x / Tc;
+    const int i = pairs ? row / P : row;
+    const int j = pairs ? row % P : row;
+    const bool have_pred = j < P;
+    const int NP = G + P;
+    const long gi = ((long)tl * NP + i) * plane_words;
+    const long pj = ((long)tl * NP + G + (have_pred ? j : 0)) * plane_words;
+    count_planes(mask, bnd, dil, gi, pj, have_pred, plane_words, counts + ((long)row * T + t0 + tl) * 6);
+}
+
+// K27b ------------------------------------------------------------------------------------------------------------------
+// The two id lists travel by value in the kernel arguments: nothing is allocated, copied or remembered for them.
+struct IdTable {
+    uint8_t obj[SOC_JF_BITS_MAX];      // label of object k, 1..254
+    uint8_t exp[SOC_JF_BITS_MAX];      // object index of expression e
+};
+
+// One wave per (frame, row, word) of the chunk.  `pred` points at the chunk's first frame of expression 0; expression e is
+// exp_stride BYTES further on; both are multiples of 8, so every word is one aligned 64-bit load.
+__global__ __launch_bounds__(256) void planes_bits_kernel(const uint8_t* __restrict__ gt, const uint8_t* __restrict__ pred,
+                                                          long exp_stride, u64* __restrict__ mask, IdTable ids, int O, int E,
+                                                          int H, int W, int WPR, int use_void, long n_words) {
+    const int lane = threadIdx.x & 63;
+    const long word = (long)blockIdx.x * 4 + (threadIdx.x >> 6);      // (frame, row, word) of this wave
+    if (word >= n_words) return;                                       // whole waves leave: the ballots below stay full
+    const int wx = (int)(word % WPR);
+    const long fy = word / WPR;                                        // frame * H + y
+    const int y = (int)(fy % H);
+    const long f = fy / H;
+    const int x = wx * 64 + lane;
+    int g = -1;                                                        // outside the image or void: in no plane
+    if (x < W) {
+        g = gt[fy * W + x];
+        if (use_void && g == 255) g = -1;
+    }
+    const u64 keep = __ballot(g >= 0);
+    const int NP = O + E;
+    for (int base = 0; base < O; base += 64) {
+        const int n = O - base < 64 ? O - base : 64;
+        u64 mine = 0;
+        for (int k = 0; k < n; ++k) {
+            const u64 b = __ballot(g == (int)ids.obj[base + k]);
+            if (lane == k) mine = b;
+        }
+        if (lane < n) mask[((f * NP + base + lane) * H + y) * WPR + wx] = mine;
+    }
+    for (int e = lane; e < E; e += 64) {                               // lane e: the word of expression e
+        const u64 p = *(const u64*)(pred + (size_t)e * exp_stride + (size_t)word * sizeof(u64));
+        mask[((f * NP + O + e) * H + y) * WPR + wx] = p & keep;
+    }
+}
+
+// One workgroup per (expression, frame of the chunk).
+__global__ __launch_bounds__(256) void counts_bits_kernel(const u64* __restrict__ mask, const u64* __restrict__ bnd,
+                                                          const u64* __restrict__ dil, int32_t* __restrict__ counts,
+                                                          IdTable ids, int O, int E, int T, int t0, int Tc, long plane_words) {
+    const int tl = blockIdx.x % Tc;
+    const int e = blockIdx.x / Tc;
+    const int NP = O + E;
+    const long gi = ((long)tl * NP + ids.exp[e]) * plane_words;
+    const long pj = ((long)tl * NP + O + e) * plane_words;
+    count_planes(mask, bnd, dil, gi, pj, true, plane_words, counts + ((long)e * T + t0 + tl) * 6);
 }
 
 inline size_t frame_bytes(int G, int P, int H, int W) {
@@ -187,6 +256,21 @@ inline int chunk_frames(int G, int P, int T, int H, int W) {
 
 inline bool sizes_ok(int G, int P, int T, int H, int W) {
     return G >= 0 && G <= 255 && P >= 0 && P <= 255 && G + P > 0 && T > 0 && H > 0 && W > 0;
+}
+
+inline DiskTable disk_table(int radius) {
+    DiskTable tab;
+    for (int dy = 0; dy <= MAX_RADIUS; ++dy) {
+        int w = 0;
+        if (dy <= radius)
+            while ((w + 1) * (w + 1) + dy * dy <= radius * radius) ++w;
+        tab.w[dy] = (uint8_t)w;
+    }
+    return tab;
+}
+
+inline bool bits_sizes_ok(int E, int O, int H, int W) {
+    return E >= 1 && E <= SOC_JF_BITS_MAX && O >= 1 && O <= SOC_JF_BITS_MAX && H > 0 && W > 0 && (long)H * W <= 0x7fffffffL;
 }
 
 }  // namespace
@@ -205,13 +289,7 @@ extern "C" int soc_davis_jf_counts_u8(const uint8_t* gt_labels, const uint8_t* p
     if (workspace_bytes < soc_davis_jf_workspace_bytes(G, P, T, H, W)) return SOC_EWORKSPACE;
     const int n_rows = pairs ? G * P : G;
     if (n_rows == 0) return SOC_OK;                                    // an empty `counts`
-    DiskTable tab;
-    for (int dy = 0; dy <= MAX_RADIUS; ++dy) {
-        int w = 0;
-        if (dy <= radius)
-            while ((w + 1) * (w + 1) + dy * dy <= radius * radius) ++w;
-        tab.w[dy] = (uint8_t)w;
-    }
+    const DiskTable tab = disk_table(radius);
     const int NP = G + P, WPR = soc_ceil_div(W, 64);
     const long plane_words = (long)H * WPR;
     const int Tc = chunk_frames(G, P, T, H, W);
@@ -233,6 +311,63 @@ extern "C" int soc_davis_jf_counts_u8(const uint8_t* gt_labels, const uint8_t* p
                            H, W, WPR, radius, tab, tiles_x, tiles_y);
         hipLaunchKernelGGL(counts_kernel, dim3((unsigned)((long)n_rows * tc)), dim3(256), 0, st, mask, bnd, dil, counts, G, P,
                            T, t0, tc, plane_words, pairs);
+        const int code = soc_check_launch();
+        if (code != SOC_OK) return code;
+    }
+    return SOC_OK;
+}
+
+extern "C" size_t soc_jf_bits_workspace_bytes(int E, int O, int H, int W) {
+    return bits_sizes_ok(E, O, H, W) ? frame_bytes(O, E, H, W) : 0;
+}
+
+extern "C" int soc_jf_counts_bits(const uint8_t* gt_labels, const uint8_t* pred_bits, long exp_stride, const int* obj_ids,
+                                  const int* exp_obj, int32_t* counts, int E, int O, int T, int H, int W, int radius,
+                                  int use_void, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!gt_labels || !pred_bits || !obj_ids || !exp_obj || !counts || !workspace || E <= 0 || O <= 0 || T <= 0 || H <= 0 ||
+        W <= 0)
+        return SOC_EINVAL;
+    if (((uintptr_t)pred_bits & 7) || (exp_stride & 7)) return SOC_EINVAL;       // the planes are read as 64-bit words
+    if (radius < 0 || radius > MAX_RADIUS || !bits_sizes_ok(E, O, H, W)) return SOC_EUNSUPPORTED;
+    const int WPR = soc_ceil_div(W, 64);
+    const long plane_words = (long)H * WPR;
+    if (exp_stride < (long)T * plane_words * (long)sizeof(u64)) return SOC_EUNSUPPORTED;
+    IdTable ids = {};
+    for (int k = 0; k < O; ++k) {
+        if (obj_ids[k] < 1 || obj_ids[k] > 254) return SOC_EUNSUPPORTED;
+        ids.obj[k] = (uint8_t)obj_ids[k];
+    }
+    for (int e = 0; e < E; ++e) {
+        if (exp_obj[e] < 0 || exp_obj[e] >= O) return SOC_EUNSUPPORTED;
+        ids.exp[e] = (uint8_t)exp_obj[e];
+    }
+    const size_t per = frame_bytes(O, E, H, W);
+    if (workspace_bytes < per) return SOC_EWORKSPACE;
+    // frames per chunk: what the workspace holds, at most CHUNK_BYTES of planes (more buys nothing and the grids stay small)
+    size_t fit = (workspace_bytes < CHUNK_BYTES ? workspace_bytes : CHUNK_BYTES) / per;
+    if (fit < 1) fit = 1;
+    const int Tc = fit < (size_t)T ? (int)fit : T;
+    const DiskTable tab = disk_table(radius);
+    const int NP = O + E;
+    const int wt = WPR < DIL_WT ? WPR : DIL_WT;
+    const int tiles_x = soc_ceil_div(WPR, wt), tiles_y = soc_ceil_div(H, DIL_BH);
+    const size_t lds = (size_t)(DIL_BH + 2 * radius) * (wt + 2) * sizeof(u64);
+    hipStream_t st = (hipStream_t)stream;
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+        const int tc = T - t0 < Tc ? T - t0 : Tc;
+        u64* mask = (u64*)workspace;
+        u64* bnd = mask + (size_t)tc * NP * plane_words;
+        u64* dil = bnd + (size_t)tc * NP * plane_words;
+        const long px_words = (long)tc * plane_words, all_words = px_words * NP;
+        hipLaunchKernelGGL(planes_bits_kernel, dim3(soc_ceil_div(px_words, 4)), dim3(256), 0, st,
+                           gt_labels + (size_t)t0 * H * W, pred_bits + (size_t)t0 * plane_words * sizeof(u64), exp_stride, mask,
+                           ids, O, E, H, W, WPR, use_void, px_words);
+        hipLaunchKernelGGL(boundary_kernel, dim3(soc_ceil_div(all_words, 256)), dim3(256), 0, st, mask, bnd, H, W, WPR,
+                           all_words);
+        hipLaunchKernelGGL(dilate_kernel, dim3((unsigned)((long)tc * NP * tiles_y * tiles_x)), dim3(256), lds, st, bnd, dil,
+                           H, W, WPR, radius, tab, tiles_x, tiles_y);
+        hipLaunchKernelGGL(counts_bits_kernel, dim3((unsigned)((long)E * tc)), dim3(256), 0, st, mask, bnd, dil, counts, ids, O,
+                           E, T, t0, tc, plane_words);
         const int code = soc_check_launch();
         if (code != SOC_OK) return code;
     }

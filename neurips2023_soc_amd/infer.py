@@ -7,6 +7,7 @@ multi-GPU form of its `sub_processor` fan-out (infer_refytb.py:84-109, SURVEY.md
     python -m torch.distributed.run --nproc-per-node 8 -m neurips2023_soc_amd.infer --clips 64 --gpus 8
     python -m neurips2023_soc_amd.infer --dataset refytb --root DATA --out RUNS [--tokenizer DIR] [--checkpoint CKPT]
     python -m neurips2023_soc_amd.infer --dataset davis --root DATA --out RUNS --make-synthetic 4   # writes DATA first
+    python -m neurips2023_soc_amd.infer --dataset refytb --root DATA --out RUNS --packed-masks --eval-refytb GT   # scores RUNS
 """
 from __future__ import annotations
 
@@ -343,6 +344,8 @@ def _run_dataset(a):
                                        n_words=a.words)
         if a.dataset == "davis" and a.eval_davis:
             synthetic_dataset.make_davis_annotations(a.root, a.eval_davis, objects=2, void=True)
+        if a.eval_refytb:
+            synthetic_dataset.make_refytb_annotations(a.root, "valid", objects=2, seed=0, void=True, out_root=a.eval_refytb)
     meta = os.path.join(a.root, "meta_expressions", "valid", "meta_expressions.json")
     for _ in range(600):                       # other ranks: the meta file is written last
         if os.path.exists(meta):
@@ -369,10 +372,16 @@ def _run_dataset(a):
         if a.dataset != "davis":
             raise RuntimeError("--eval-davis scores the output of --dataset davis")
         extra.update(eval_root=a.eval_davis, eval_task=a.eval_task)
+    if a.eval_refytb:
+        extra.update(eval_root=a.eval_refytb)
     for _ in range(max(a.repeat, 1)):
         stats = driver.run(model, tokenize, a.root, a.out, rank, world, dev, engine=engine, **extra)
     stats["clips_per_s"] = stats["expressions"] / stats["seconds"]
-    if "jf" in stats:
+    if "jf" in stats and "global" in stats["jf"]:
+        jf = stats["jf"]
+        print(" ".join(f"{h:>9}" for h in jf["measures"]))
+        print(" ".join(f"{x:9.5f}" for x in jf["global"]))
+    elif "jf" in stats:
         jf = stats["jf"]
         print(" " * 7 + " ".join(f"{h:>9}" for h in jf["measures"]))
         for name, row in [(f"anno_{i}", r) for i, r in enumerate(jf["per_annotator"])] + [("mean", jf["mean"])]:
@@ -406,6 +415,10 @@ def parse_args(argv=None):
                          "ground truth is written to DIR first")
     ap.add_argument("--eval-task", default="unsupervised", choices=["semi-supervised", "unsupervised"],
                     help="--eval-davis: the DAVIS task (the reference's eval_davis.py default: unsupervised)")
+    ap.add_argument("--eval-refytb", metavar="DIR",
+                    help="--dataset refytb: score every expression's masks against the tree DIR (valid/Annotations and a "
+                         "meta_expressions.json whose expressions carry obj_id) on the device and write the per-expression J&F CSVs "
+                         "into --out; with --make-synthetic a synthetic ground truth is written to DIR first")
     ap.add_argument("--packed-masks", action="store_true",
                     help="--dataset refytb: masks leave the GPU bit-packed (one bit per pixel, packed_masks.py) and the PNG files are "
                          "encoded from the bits; same files as without the flag")
@@ -417,6 +430,8 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.packed_masks and a.dataset != "refytb":
         ap.error("--packed-masks applies to --dataset refytb (the DAVIS driver writes label maps, which are not one-bit data)")
+    if a.eval_refytb and a.dataset != "refytb":
+        ap.error("--eval-refytb scores the output of --dataset refytb (--eval-davis is the flag of --dataset davis)")
     if a.group is None:
         a.group = 8 if a.graphs else 1
     a.gpus_given = a.gpus is not None

@@ -65,6 +65,75 @@ def load_meta(root: str, split: str = "valid"):
         return img_folder, json.load(f)["videos"]
 
 
+class _Scorer:
+    """Per-expression J&F (refytb_eval, K27b) of the masks against a ground-truth tree, while they are still on the device.  A
+    video's label maps are decoded once, on a reader thread from the moment the driver reaches the video, uploaded when its
+    first expression arrives and dropped after its last.  Nothing is waited for here: the counts stay on the device until
+    finish()."""
+
+    def __init__(self, eval_root: str, split: str, videos: Sequence[str], device):
+        from . import refytb_eval
+        self.re, self.split, self.device = refytb_eval, split, device
+        self.dataset = refytb_eval.RefYtbDataset(eval_root, split, videos)
+        self.obj_of = {v: dict(self.dataset.expressions(v)) for v in self.dataset.videos}     # a missing obj_id raises here
+        self.gt = {}                # video -> [labels on the device, expressions still to come]
+        self.expected = {}          # video -> expressions the driver will send
+        self.reader = ThreadPoolExecutor(max_workers=2)
+        self.reading = {}           # video -> future of its label maps (PNG decoding beside the forwards)
+        self.scored = []            # (video, exp_ids, obj_ids, counts [E,T,6] on the device), in arrival order
+
+    def begin(self, video: str, expressions: int) -> None:
+        self.expected[video] = expressions
+        if expressions and video not in self.reading and video not in self.gt:
+            self.reading[video] = self.reader.submit(self.dataset.masks, video)
+
+    @staticmethod
+    def in_place(bits: Sequence[torch.Tensor]):
+        """Packed masks of several expressions -> (pred_bits, exp_stride) for jf_bits.jf_counts_bits: the first one's view and
+        the distance in bytes when they lie evenly spaced in one buffer (the slices of a group's K6b output), a stacked copy
+        otherwise."""
+        first = bits[0]
+        if len(bits) == 1:
+            return (first, None) if first.is_contiguous() and first.data_ptr() % 8 == 0 else (first.contiguous().clone()[None], None)
+        step = bits[1].data_ptr() - first.data_ptr()
+        even = all(b.is_contiguous() and b.shape == first.shape and b.data_ptr() == first.data_ptr() + k * step
+                   and b.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() for k, b in enumerate(bits))
+        if even and step >= first.numel() and step % 8 == 0 and first.data_ptr() % 8 == 0:
+            return first, step
+        return torch.stack(list(bits)), None
+
+    def score(self, video: str, exp_ids: Sequence[str], bits: Sequence[torch.Tensor], width: int) -> None:
+        """bits: one packed uint8 [T,H0,RB] mask tensor per expression of `video`, all scored in ONE call."""
+        if video not in self.gt:
+            maps = self.reading.pop(video).result()
+            self.gt[video] = [torch.from_numpy(maps).to(self.device), self.expected[video]]
+        entry = self.gt[video]
+        gt = entry[0]
+        want = (gt.shape[0], gt.shape[1], 8 * (-(-gt.shape[2] // 64)))
+        if tuple(bits[0].shape) != want or int(width) != gt.shape[2]:
+            raise ValueError(f"{video}: ground truth {tuple(gt.shape)} does not match the output "
+                             f"({bits[0].shape[0]}, {bits[0].shape[1]}, {int(width)}) (frames, height, width)")
+        for exp_id in exp_ids:
+            if exp_id not in self.obj_of[video]:
+                raise KeyError(f"{self.dataset.meta_path}: videos['{video}']['expressions'] has no '{exp_id}'")
+        obj_ids = [self.obj_of[video][e] for e in exp_ids]
+        pred, stride = self.in_place(bits)
+        self.scored.append((video, list(exp_ids), obj_ids, self.re.video_counts(gt, obj_ids, pred, exp_stride=stride)))
+        entry[1] -= len(exp_ids)
+        if entry[1] <= 0:
+            del self.gt[video]
+
+    def finish(self, out_dir: str) -> Dict:
+        self.reader.shutdown()
+        result = self.re.RefYtbJF()
+        for video, exp_ids, obj_ids, counts in self.scored:
+            result.add_counts(video, exp_ids, obj_ids, counts.cpu().numpy())
+        os.makedirs(out_dir, exist_ok=True)
+        self.re.write_csvs(result, out_dir, self.split)
+        return {"measures": list(self.re.G_MEASURES), "global": result.global_row(),
+                "per_expression": [list(r) for r in result.per_expression()]}
+
+
 PREFETCH_VIDEOS = 4          # videos decoded ahead of the one on the GPU (a 720p clip of 8 frames is 22 MB of pinned staging)
 
 
@@ -73,14 +142,24 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         split: str = "valid", size: int = 360, max_size: Optional[int] = 640, use_graphs: bool = False,
         decode_workers: int = 8, writer_workers: int = 16, videos: Optional[Sequence[str]] = None,
         engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1,
-        packed_masks: bool = False) -> Dict:
-    """Process this rank's videos; returns counters + timings.  packed_masks: the masks leave the GPU one bit per pixel (K6b, once
+        packed_masks: bool = False, eval_root: Optional[str] = None) -> Dict:
+    """Process this rank's videos; returns counters + timings.  eval_root: a tree with <split>/Annotations and a
+    meta_expressions.json whose expressions carry obj_id.  When given, every expression's masks are scored against the object it
+    names while they are on the device (refytb_eval, K27b: the bits K6b wrote are read in place, the expressions of one video
+    that arrive in one group in one call; byte masks are packed on the device first): stats["jf"] holds the global row and the
+    per-expression rows, and the two CSVs are written into out_dir.  The PNGs and everything else the driver does are the same
+    with and without it.  packed_masks: the masks leave the GPU one bit per pixel (K6b, once
     per group of one original size), the pinned buffers and the host copy are [T,H0,RB] uint8 -- an eighth -- and the writers encode
     the PNGs from the bits; the files are the same.  group > 1 (with use_graphs): consecutive clips of one
     geometry share every launch of the forward, each still getting its single-clip result (ClipInferencer(group=...)).  `tokenize(expression) -> int64 [1,L]`
     (RobertaTokenizerFast in production; no vocabulary files exist offline, so the caller supplies it)."""
     img_folder, data = load_meta(root, split)
     todo = split_videos(sorted(data.keys()) if videos is None else list(videos), rank, world)
+    scorer = None
+    if eval_root is not None:
+        if world != 1:
+            raise ValueError("eval_root: the tables cover every video of the set, so scoring runs in one process (world = 1)")
+        scorer = _Scorer(eval_root, split, todo, device)
     engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group,
                                       packed_masks=packed_masks)
     if bool(getattr(engine, "packed_masks", False)) != bool(packed_masks):
@@ -121,7 +200,7 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
 
     def enqueue_download(res):
         """masks of a finished clip -> pinned host buffer on the d2h stream; returns the job for flush()"""
-        save_dir, names = res["tag"]
+        save_dir, names = res["tag"][:2]
         masks, width = (res["masks_packed"], res["mask_size"][1]) if packed_masks else (res["masks"], None)
         host = host_buffer(masks.shape, enqueue_download.n % (2 * lag + 2), masks.dtype)
         enqueue_download.n += 1
@@ -137,11 +216,32 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
     import collections
     jobs = collections.deque()           # downloads in flight, oldest first
 
+    def score(results):
+        """the results of one replay (or one eager call), video by video: each video's expressions in one call"""
+        t3 = time.perf_counter()
+        i = 0
+        while i < len(results):
+            video = results[i]["tag"][2]
+            j = i
+            while j < len(results) and results[j]["tag"][2] == video:
+                j += 1
+            run = results[i:j]
+            if packed_masks:
+                bits, width = [r["masks_packed"] for r in run], run[0]["mask_size"][1]
+            else:
+                from . import packed_masks as PM
+                bits, width = [PM.pack(r["masks"]) for r in run], run[0]["masks"].shape[-1]
+            scorer.score(video, [r["tag"][3] for r in run], bits, width)
+            i = j
+        stats["seconds_eval"] = stats.get("seconds_eval", 0.0) + time.perf_counter() - t3
+
     def handle(results):
         for res in results:
             jobs.append(enqueue_download(res))
             while len(jobs) > lag:
                 flush(jobs.popleft())
+        if scorer is not None and results:
+            score(results)
 
     with ThreadPoolExecutor(max_workers=writer_workers) as writers:
         for vi, video in enumerate(todo):
@@ -154,6 +254,8 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
                 if vi + ahead < len(todo):
                     nxt = todo[vi + ahead]
                     cache.prefetch(clip_io.frame_paths(img_folder, nxt, data[nxt]["frames"]))
+            if scorer is not None:
+                scorer.begin(video, len(data[video]["expressions"]))
             for exp_id, item in data[video]["expressions"].items():
                 t1 = time.perf_counter()
                 clip, orig = cache.get(paths)                                  # decoded / resized once per video
@@ -162,10 +264,10 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
                 save_dir = os.path.join(out_dir, video, exp_id)
                 os.makedirs(save_dir, exist_ok=True)
                 if streaming:
-                    handle(engine.submit(clip, ids, (save_dir, frames), orig))  # results of the PREVIOUS replay, if any
+                    handle(engine.submit(clip, ids, (save_dir, frames, video, exp_id), orig))  # results of the PREVIOUS replay, if any
                 else:
                     res = engine(clip, ids, orig)                              # [T,H0,W0] bool, still in flight
-                    res["tag"] = (save_dir, frames)
+                    res["tag"] = (save_dir, frames, video, exp_id)
                     handle([res])
                 stats["seconds_input"] += t2 - t1
                 stats["seconds_model"] += time.perf_counter() - t2
@@ -184,4 +286,6 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
     cache.close()
     stats.update(seconds=time.perf_counter() - t0, cache_hits=cache.hits, cache_misses=cache.misses)
     stats.update({k: v for k, v in getattr(engine, "stats", {}).items()})       # group replays, part-filled ones, remainders
+    if scorer is not None:
+        stats["jf"] = scorer.finish(out_dir)
     return stats

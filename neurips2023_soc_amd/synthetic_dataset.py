@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -165,3 +165,37 @@ def make_davis_annotations(root: str, davis_root: str, objects: int = 2, void: b
                 png.putpalette(palette)
                 png.save(os.path.join(d, f"{t:05d}.png"))
     return davis_root
+
+
+def make_refytb_annotations(root: str, split: str = "valid", objects: int = 2, seed: int = 0, void: bool = False,
+                            out_root: Optional[str] = None) -> str:
+    """A Ref-YouTube-VOS-layout ground truth for the videos of a make_dataset tree under `root`, so that the driver's output
+    can be scored offline (refytb_eval): palette PNGs of seeded blob label maps (blob_label_maps) as
+    <split>/Annotations/<video>/<frame>.png, and an "obj_id" in every expression of meta_expressions.json -- expression k of a
+    video names object 1 + k % objects, so several expressions share an object once there are more expressions than objects.
+    out_root: write the annotations and the completed JSON there instead and leave `root` as it is.  Stand-in data: the scores
+    say nothing about a model."""
+    from PIL import Image
+    from .infer_davis import davis_palette
+    out_root = root if out_root is None else out_root
+    with open(os.path.join(root, "meta_expressions", split, "meta_expressions.json")) as f:
+        meta = json.load(f)
+    palette = davis_palette()
+    for v, name in enumerate(sorted(meta["videos"])):
+        names = meta["videos"][name]["frames"]
+        with Image.open(os.path.join(root, split, "JPEGImages", name, names[0] + ".jpg")) as img:
+            width, height = img.size
+        maps = blob_label_maps(seed * 1000 + v, len(names), height, width, objects, void=void)
+        d = os.path.join(out_root, split, "Annotations", name)
+        os.makedirs(d, exist_ok=True)
+        for t, frame in enumerate(names):
+            png = Image.fromarray(maps[t])
+            png.putpalette(palette)
+            png.save(os.path.join(d, frame + ".png"))
+        for k, item in enumerate(meta["videos"][name]["expressions"].values()):
+            item["obj_id"] = 1 + k % objects
+    mdir = os.path.join(out_root, "meta_expressions", split)
+    os.makedirs(mdir, exist_ok=True)
+    with open(os.path.join(mdir, "meta_expressions.json"), "w") as f:
+        json.dump(meta, f)
+    return out_root
