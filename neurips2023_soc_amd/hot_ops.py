@@ -1,4 +1,4 @@
-"""Host-side entry points of the HIP kernels K1-K19 (torch tensors in, torch tensors out).
+"""Host-side entry points of the HIP kernels (K1 ... K27; torch tensors in, torch tensors out).
 
 Every function requires CUDA(=HIP) tensors and calls straight into libsoc_hip.so through the C
 ABI of include/soc_hip.h on torch's current stream.  There is deliberately no fallback: CPU
@@ -867,11 +867,11 @@ def ws_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, ln: Opti
 # ---------------------------------------------------------------------------------------------
 # K20: f32 linear layers on the bf16 matrix cores by exact operand splitting
 
-# The arithmetic mode of a forward and the routing rules that hang on it live in matmul_mode.py, the cache of packed weight images
-# in derived_cache.py; both are re-exported here (callers and tests use hot_ops.<name>).
+# The arithmetic mode of a forward lives in matmul_mode.py, the cache of packed weight images in derived_cache.py; both are
+# re-exported here (callers and tests use hot_ops.<name>).  So is split_wins of linear_routes.py, at the end of this file.
 from .derived_cache import DerivedCache, hold, keep_alive  # noqa: E402,F401
-from .matmul_mode import (DEFAULT_MATMUL_MODE, _SPLIT_OFF, _mode_tls, k1_split_enabled, k13_split_enabled,  # noqa: E402,F401
-                          matmul_mode, split_enabled, split_wins, use_matmul_mode)
+from .matmul_mode import (DEFAULT_MATMUL_MODE, _mode_tls, k1_split_enabled, k13_split_enabled,  # noqa: E402,F401
+                          matmul_mode, split_enabled, split_off, use_matmul_mode)
 
 
 _SPLIT_ACT = {"none": 0, "relu": 1, "gelu": 2}
@@ -991,7 +991,7 @@ def xs_linear_supported(x, weight) -> bool:
     ctp = 2 if K <= 256 else 1
     top = 8 if K > 768 else 18              # K = 1024 keeps 384 registers of x fragments: ranges of at most 8 column tiles
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and split_enabled()
-            and "k24" not in _SPLIT_OFF and x.shape[-1] == K and K in XS_LINEAR_K and N % 32 == 0
+            and not split_off("k24") and x.shape[-1] == K and K in XS_LINEAR_K and N % 32 == 0
             and any((N // 16) % n == 0 and n % ctp == 0 and n <= top for n in _XS_NCT))
 
 
@@ -1091,7 +1091,7 @@ def mlp_split_supported(x: Tensor, w1: Tensor, w2: Tensor) -> bool:
     """K23 takes act(LN(x) w1^T + b1) w2^T + b2 (+ residual): CUDA fp32, model width 96 / 128 / 192 / 256 / 384 / 512, hidden width a
     multiple of 32 up to mlp_split_max_hidden(width), split arithmetic on (SOC_SPLIT_OFF=mlp switches it off)."""
     Cw = x.shape[-1]
-    return (x.is_cuda and x.dtype == torch.float32 and split_enabled() and "mlp" not in _SPLIT_OFF and Cw in MLP_SPLIT_C
+    return (x.is_cuda and x.dtype == torch.float32 and split_enabled() and not split_off("mlp") and Cw in MLP_SPLIT_C
             and tuple(w1.shape[1:]) == (Cw,) and tuple(w2.shape) == (Cw, w1.shape[0]) and w1.shape[0] % 32 == 0
             and w1.shape[0] <= mlp_split_max_hidden(Cw)
             and w1.dtype == torch.float32 and w2.dtype == torch.float32)
@@ -1239,3 +1239,8 @@ def linear_split(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
                                       int(split_at or 0), M, N, K, _SPLIT_ACT[act], cfg, _stream())
     _lib.check(rc, "soc_linear_split_f32")
     return out if out2 is None else (out, out2)
+
+
+# A cycle, kept only so that `hot_ops.split_wins` (bench.py, tools, tests) still resolves: linear_routes.py imports this module for
+# the *_supported predicates above, so it can be imported only down here, once they exist; nothing in this module calls it
+from .linear_routes import split_wins  # noqa: E402,F401

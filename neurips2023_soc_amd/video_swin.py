@@ -10,7 +10,6 @@ that exists here.  Module / parameter names follow the reference so its checkpoi
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -19,6 +18,7 @@ from torch import nn
 
 from . import fused, hot_ops
 from .derived_cache import hold
+from .linear_routes import plan_stage
 from .nested_tensor import NestedTensor
 from .position_encoding import PositionEmbeddingSine2D
 
@@ -56,13 +56,14 @@ class WindowAttention3D(nn.Module):
         self.proj = nn.Linear(dim, dim)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
 
-    def forward(self, x: torch.Tensor, shift: Sequence[int], residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,D,H,W,C] (after norm1, un-padded) -> attention branch output [B,D,H,W,C] (+ residual: the block's
-        shortcut, added in the projection's epilogue where a hand-written kernel runs it: fused.route_linear)."""
-        qkv = fused.linear(x, self.qkv.weight, self.qkv.bias)           # stage 2: K24 (K13b with SOC_SPLIT_OFF=k24)
+    def forward(self, x: torch.Tensor, shift: Sequence[int], residual: Optional[torch.Tensor] = None, plan=None, ln=None) -> torch.Tensor:
+        """x [B,D,H,W,C] (after norm1, or with norm1 as `ln` for the qkv launch to apply; un-padded) -> attention branch output
+        [B,D,H,W,C] (+ residual: the block's shortcut, added in the projection's epilogue where a hand-written kernel runs it);
+        `plan`: the stage's StagePlan."""
+        qkv = fused.linear(x, self.qkv.weight, self.qkv.bias, ln=ln, route=plan and plan.qkv)
         attn = hot_ops.window_attention3d(qkv, self.qkv.bias, self.relative_position_bias_table,
                                           self.num_heads, self.window_size, shift)
-        return fused.linear(attn, self.proj.weight, self.proj.bias, residual=residual)
+        return fused.linear(attn, self.proj.weight, self.proj.bias, residual=residual, route=plan and plan.proj)
 
 
 class Mlp(nn.Module):
@@ -71,8 +72,8 @@ class Mlp(nn.Module):
         self.fc1 = nn.Linear(dim, hidden)
         self.fc2 = nn.Linear(hidden, dim)
 
-    def forward(self, x):
-        return self.fc2(fused.linear_gelu(x, self.fc1))
+    def forward(self, x, plan=None):
+        return self.fc2(fused.linear(x, self.fc1.weight, self.fc1.bias, act="gelu", route=plan and plan.fc1))
 
 
 class SwinTransformerBlock3D(nn.Module):
@@ -100,84 +101,48 @@ class BasicLayer(nn.Module):
             SwinTransformerBlock3D(dim, num_heads, window_size, (0, 0, 0) if i % 2 == 0 else shift)
             for i in range(depth)])
         self.downsample = None
+        # (token map's shape, dtype, device, arithmetic mode) -> StagePlan.  plan_stage also routes the layers, which costs 15-46 us a
+        # call where the flow decision alone took 7-17; an eager forward asks once per geometry instead of once per stage and step
+        self._plans = {}
         self.out_tag = None     # "swin<stage>": the stage's last K23 launch writes into hot_ops.placed(out_tag) when one is set
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:  # [B,D,H,W,C] token-major throughout
-        """Tall stages with a short channel width (stages 0-1 of every Video-Swin variant) run each block as four
-        K13 launches around K1 -- norm1 + qkv | K1 | proj + residual | norm2 + fc1 + GELU | fc2 + residual -- so no
-        LayerNorm-ed or GELU-ed copy of the token map is ever a separate pass.  Elsewhere every residual add is fused
-        with the LayerNorm that consumes its result (K5): x += attn -> norm2, x += mlp -> next block's norm1.  Same
-        values as block-by-block."""
+        """Runs the blocks as linear_routes.plan_stage says (StagePlan names the flows).  "ws" / "k20" / "k24": a block is norm1 + qkv |
+        K1 | proj + shortcut | norm2 + fc1 + GELU | fc2 + shortcut on the kernels of the plan, or one K23 launch for the last two: no
+        LayerNorm-ed or GELU-ed copy of the token map is a separate pass.  "k23" / "k5": one LayerNorm pass at the stage's entry, then every
+        shortcut add rides with the LayerNorm that consumes its result (x += attn -> norm2, x += mlp -> next norm1), in K23 or K5."""
         blocks = self.blocks
-        flow = self.stage_flow(x)
-        if flow == "k20":
-            # K20 (bf16 matrix cores, exact three-way split): LayerNorm folded into the layer, GELU / residual in its
-            # epilogue -- norm1 + qkv | K1 | proj + residual | norm2 + fc1 + GELU | fc2 + residual
+        key = (x.shape, x.dtype, x.device, hot_ops.matmul_mode())
+        plan = self._plans.get(key) or self._plans.setdefault(key, plan_stage(x, blocks[0]))
+        if plan.flow in ("ws", "k20", "k24"):
             for blk in blocks:
-                a, m = blk.attn, blk.mlp
-                qkv = hot_ops.linear_split(x, a.qkv.weight, a.qkv.bias, ln=(blk.norm1.weight, blk.norm1.bias, blk.norm1.eps))
-                o = hot_ops.window_attention3d(qkv, a.qkv.bias, a.relative_position_bias_table, a.num_heads,
-                                               a.window_size, blk.shift_size)
-                x = hot_ops.linear_split(o, a.proj.weight, a.proj.bias, residual=x)
-                if fused.mlp_ok(x, m.fc1, m.fc2):      # C = 256 (Swin-B stage 1): norm2 + fc1 + GELU + fc2 + shortcut in one K23 launch
-                    x = hot_ops.mlp_split(x, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, "gelu",
-                                          ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), residual=x,
-                                          out=hot_ops.placed(self.out_tag, x) if blk is blocks[-1] else None)
+                m = blk.mlp
+                x = blk.attn(x, blk.shift_size, residual=x, plan=plan, ln=_ln(blk.norm1))
+                if plan.mlp == "k23":
+                    # norm2 + fc1 + GELU + fc2 + shortcut in one launch, the hidden layer never leaves the registers
+                    x = hot_ops.mlp_split(x, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, "gelu", ln=_ln(blk.norm2),
+                                          residual=x, out=hot_ops.placed(self.out_tag, x) if blk is blocks[-1] else None)
                     continue
-                h = hot_ops.linear_split(x, m.fc1.weight, m.fc1.bias, ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps),
-                                         act="gelu")
-                if _FORCE_SPLIT_FLOW:
-                    x = hot_ops.linear_split(h, m.fc2.weight, m.fc2.bias, residual=x)
-                else:
-                    x = fused.linear(h, m.fc2.weight, m.fc2.bias, residual=x)  # K20 or library + add (split_wins)
-            return x
-        if flow == "ws":
-            for blk in blocks:
-                a = blk.attn
-                qkv = hot_ops.ws_linear(x, a.qkv.weight, a.qkv.bias, ln=(blk.norm1.weight, blk.norm1.bias, blk.norm1.eps))
-                o = hot_ops.window_attention3d(qkv, a.qkv.bias, a.relative_position_bias_table, a.num_heads,
-                                               a.window_size, blk.shift_size)
-                x = hot_ops.ws_linear(o, a.proj.weight, a.proj.bias, residual=x)
-                if fused.mlp_ok(x, blk.mlp.fc1, blk.mlp.fc2):
-                    # K23: norm2 + fc1 + GELU + fc2 + residual in one launch, the hidden layer never leaves the registers
-                    x = hot_ops.mlp_split(x, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, "gelu",
-                                          ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), residual=x,
-                                          out=hot_ops.placed(self.out_tag, x) if blk is blocks[-1] else None)
-                    continue
-                h = hot_ops.ws_linear(x, blk.mlp.fc1.weight, blk.mlp.fc1.bias,
-                                      ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), act="gelu")
-                if hot_ops.ws_linear_supported(h, blk.mlp.fc2.weight, False):
-                    x = hot_ops.ws_linear(h, blk.mlp.fc2.weight, blk.mlp.fc2.bias, residual=x)
-                else:
-                    x = x + blk.mlp.fc2(h)
-            return x
-        if flow == "k24":
-            for blk in blocks:
-                a, m = blk.attn, blk.mlp
-                qkv = hot_ops.xs_linear(x, a.qkv.weight, a.qkv.bias, ln=(blk.norm1.weight, blk.norm1.bias, blk.norm1.eps))
-                o = hot_ops.window_attention3d(qkv, a.qkv.bias, a.relative_position_bias_table, a.num_heads,
-                                               a.window_size, blk.shift_size)
-                x = hot_ops.xs_linear(o, a.proj.weight, a.proj.bias, residual=x)
-                h = hot_ops.xs_linear(x, m.fc1.weight, m.fc1.bias, ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), act="gelu")
-                x = fused.linear(h, m.fc2.weight, m.fc2.bias, residual=x)
+                h = fused.linear(x, m.fc1.weight, m.fc1.bias, ln=_ln(blk.norm2), act="gelu", route=plan.fc1)
+                x = fused.linear(h, m.fc2.weight, m.fc2.bias, residual=x, route=plan.fc2)
             return x
         _, h = hot_ops.add_layernorm(x, None, blocks[0].norm1.weight, blocks[0].norm1.bias, blocks[0].norm1.eps)
-        if flow == "k23":
+        if plan.flow == "k23":
             # stage 2 (C = 384): the shortcut rides in the projection's epilogue, norm2 + fc1 + GELU + fc2 + shortcut are one K23
             # launch that also emits norm1 of the next block: no LayerNorm pass inside the stage
             for i, blk in enumerate(blocks):
-                x = blk.attn(h, blk.shift_size, residual=x)
+                x = blk.attn(h, blk.shift_size, residual=x, plan=plan)
                 m = blk.mlp
                 nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else None
                 y = hot_ops.mlp_split(x, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, "gelu",
-                                      ln=(blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), residual=x,
-                                      post_ln=None if nxt is None else (nxt.weight, nxt.bias, nxt.eps), return_sum=nxt is not None)
+                                      ln=_ln(blk.norm2), residual=x,
+                                      post_ln=None if nxt is None else _ln(nxt), return_sum=nxt is not None)
                 x, h = y if nxt is not None else (y, None)        # norm1 of the next block leaves in the same launch
             return x
         for i, blk in enumerate(blocks):
-            a = blk.attn(h, blk.shift_size)
+            a = blk.attn(h, blk.shift_size, plan=plan)
             x, h = hot_ops.add_layernorm(x, a, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            m = blk.mlp(h)
+            m = blk.mlp(h, plan)
             if i + 1 < len(blocks):
                 nxt = blocks[i + 1].norm1
                 x, h = hot_ops.add_layernorm(x, m, nxt.weight, nxt.bias, nxt.eps)
@@ -185,61 +150,9 @@ class BasicLayer(nn.Module):
                 x = x + m
         return x
 
-    def stage_flow(self, x) -> str:
-        """How the blocks of this stage run (shapes, dtypes and devices only -- tests/test_routes.py pins it per configuration):
-        "ws"  K13b launches around K1, LayerNorms in their prologues, the MLP as one K23 launch where K23 covers the width
-              (tall stages of width 96 / 128 / 192: stages 0-1 of Swin-T / -S, stage 0 of Swin-B);
-        "k20" every layer on K20, LayerNorm folded into the packed weights (tall stages wider than that: Swin-B stage 1, and
-              stage 1 of the others with SOC_SPLIT_OFF=k13);
-        "k23" one LayerNorm pass at the stage's entry, then per block qkv | K1 | proj + shortcut | K23 (norm2 + MLP + shortcut +
-              norm1 of the next block): stage 2 of Swin-T / -S (C = 384) and of Swin-B (C = 512);
-        "k24" norm1 + qkv | K1 | proj + shortcut | norm2 + fc1 + GELU as K24 launches (LayerNorm in their prologues), fc2 + shortcut
-              through fused.linear: stage 3 (C = 768, Swin-B 1024; the hidden width 4 C is beyond K24);
-        "k5"  every shortcut add fused with the LayerNorm that consumes it (K5), GEMMs per fused.route_*: the rest."""
-        blk = self.blocks[0]
-        # stage 1 (C = 192) in the split arithmetic: K13b beats K20 on qkv / proj / fc1 (49 / 24 / 71 against 60 / 30 / 74 us,
-        # tools/experiments/k13b_time.py); with SOC_SPLIT_OFF=k13 the K20 flow takes it
-        prefer_ws = hot_ops.k13_split_enabled() and x.shape[-1] in hot_ops.WS_SPLIT_LN_K and self._weight_stationary(x)
-        # C = 384 / 512 keep the "k23" flow however many rows a launch group brings (four clips: 29 440): K24 qkv 161 us against
-        # K20 + LayerNorm 229, K23 with norm1 of the next block 392 against 415 + a LayerNorm in the next qkv
-        # (tools/experiments/stage2_group_flow.py); the "k20" flow is for the tall stages K24 / K23 do not cover that way
-        prefer_k23 = (x.shape[-1] in (384, 512) and fused.mlp_ok(x, blk.mlp.fc1, blk.mlp.fc2)
-                      and all(fused.xs_ok(x, w) for w in (blk.attn.qkv.weight, blk.attn.proj.weight)))
-        if not prefer_ws and not prefer_k23 and self._split_flow(x):
-            return "k20"
-        if self._weight_stationary(x):
-            return "ws"
-        if fused.mlp_ok(x, blk.mlp.fc1, blk.mlp.fc2):
-            return "k23"
-        if (x.shape[-1] in (768, 1024) and x.numel() // x.shape[-1] >= 1024
-                and all(hot_ops.xs_linear_supported(x, w) for w in (blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc1.weight))):
-            return "k24"
-        return "k5"
 
-    def _split_flow(self, x: torch.Tensor) -> bool:
-        """Tall stages wider than K13's sweet spot (C >= 192: stage 1 of Swin-T / -S, stages 1 of Swin-B): every layer on
-        K20 (tools/split_probe.py: 66 / 29 / 80 us against 75 / 36 / 99-108 us for K13 at Swin-T stage 1)."""
-        blk = self.blocks[0]
-        C = x.shape[-1]
-        rows = x.numel() // C
-        if _FORCE_SPLIT_FLOW:       # experiment switch (tools/experiments/README.md): every stage with rows >= the value
-            return (x.is_cuda and x.dtype == torch.float32 and C >= 192 and rows >= _FORCE_SPLIT_FLOW
-                    and hot_ops.split_enabled()
-                    and hot_ops.linear_split_supported(x, blk.attn.qkv.weight, True))
-        return (x.is_cuda and x.dtype == torch.float32 and C >= 192 and rows >= 16384
-                and hot_ops.split_wins(rows, 3 * C, C, 1, "swin") and hot_ops.split_wins(rows, C, C, 1, "swin")
-                and hot_ops.linear_split_supported(x, blk.attn.qkv.weight, True))
-
-    def _weight_stationary(self, x: torch.Tensor) -> bool:
-        """K13 pays where the token map is tall and the weights of a layer fit a CU's LDS in a few column ranges."""
-        blk = self.blocks[0]
-        return (x.is_cuda and x.numel() // x.shape[-1] >= 16384
-                and hot_ops.ws_linear_supported(x, blk.attn.qkv.weight, True)
-                and hot_ops.ws_linear_supported(x, blk.attn.proj.weight, False)
-                and hot_ops.ws_linear_supported(x, blk.mlp.fc1.weight, True))
-
-
-_FORCE_SPLIT_FLOW = int(os.environ.get("SOC_FORCE_SPLIT_FLOW_ROWS", "0"))
+def _ln(norm: nn.LayerNorm):
+    return norm.weight, norm.bias, norm.eps
 
 
 class PatchMerging(nn.Module):
