@@ -528,6 +528,91 @@ def group_pipeline_class(clips: int):
     return type(f"Group{clips}PipelinedClipGraph", (PairPipelinedClipGraph,), {"CLIPS": int(clips)})
 
 
+class SharedVideoPipelinedClipGraph(PairPipelinedClipGraph):
+    """The group pipeline for ONE clip and CLIPS expressions of it per replay (shared_group_pipeline_class).
+
+    Everything of the head in front of the first vision-language fusion is a function of the frames alone (Video-Swin, the
+    position encodings, input_proj + GroupNorm, vlf's query projection, lvf's key / value projections): the head here runs it
+    once (SOC.forward_video_shared) and joins it with the text state of the CLIPS token rows (SOC.forward_fuse_encode_shared,
+    vlf's core on K3s).  From the deformable encoder on the replay is that of a launch group of CLIPS clips: same hand-over
+    state, same tail (group_tail), same [CLIPS, R] record, same double buffering and flush.  Row s of the record is expression
+    s of the clip staged for that replay, equal to the one-clip pipeline's record of (clip, expression s) to f32 rounding.
+
+        g.stage_video(clip)                       # once per replay
+        g.stage_inputs(ids_s, attn_s, slot=s)     # per expression; a slot that is not staged keeps its previous tokens
+        recs = g.replay()                         # [CLIPS, R] of the replay before, or None
+        rest = g.flush()
+    """
+
+    def _allocate(self, model, T: int, H: int, W: int, L: int, device) -> None:
+        super()._allocate(model, T, H, W, L, device)
+        dev = self.device
+        self.clip = torch.zeros(1, T, 3, H, W, device=dev).transpose(0, 1)                     # ONE clip [T,1,3,H,W]
+        self.pad = torch.zeros(1, T, H, W, dtype=torch.bool, device=dev).transpose(0, 1)
+        if self.record.dim() == 1:                                                             # one slot: still a [1, R] group record
+            self.record = self.record[None]
+
+    def _head(self, fork: bool):
+        model, dev = self.model, self.device
+        if fork:                                   # RoBERTa beside Video-Swin, as SOC.forward_backbone forks them
+            main, side = torch.cuda.current_stream(dev), model._side_stream(dev)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                tx = model.forward_text_state(self._tokens(), dev)
+            vs = model.forward_video_shared(self._samples())
+            main.wait_stream(side)
+        else:
+            tx = model.forward_text_state(self._tokens(), dev)
+            vs = model.forward_video_shared(self._samples(), fork=False)
+        return model.forward_fuse_encode_shared(vs, tx, fork=fork, feats0_out=getattr(self, "_feats0_dst", None))
+
+    def _placed(self, body, dst, tags):
+        """As the parent's for the encoder memory.  The stage-0 token map is produced for ONE clip and the hand-over state holds
+        it once per slot: Video-Swin writes it into the first slot of dst and the head copies that slot into the others (one slot:
+        no copy at all, as in the one-clip pipeline)."""
+        f0 = self._feats0_dst = dst["feats0"]
+        n, c, h, w = f0.shape
+        tok = f0.permute(0, 2, 3, 1)
+        try:
+            if "swin0" in tags and tok.is_contiguous():
+                hot_ops.place_output("swin0", tok.view(self.CLIPS, self.T, h, w, c)[:1])
+            return super()._placed(body, dst, tuple(t for t in tags if t != "swin0"))
+        finally:
+            hot_ops.place_output("swin0", None)
+            self._feats0_dst = None
+
+    def stage_video(self, clip: torch.Tensor) -> None:
+        """Copy the clip [T,3,H,W] (or [T,1,3,H,W]) into the static input, on the current stream; the caller's tensor is free
+        after the call."""
+        dst = self.clip[:, 0]
+        dst.copy_(clip.view(dst.shape), non_blocking=True)
+
+    def stage_inputs(self, ids: torch.Tensor, attn: Optional[torch.Tensor] = None, slot: int = 0) -> None:
+        """Token ids / attention mask [1,L] or [L] of ONE expression into slot `slot` (0 .. CLIPS - 1); the mask is ones when
+        omitted."""
+        self.ids[slot].copy_(ids.view(-1), non_blocking=True)
+        if attn is not None:
+            self.attn[slot].copy_(attn.view(-1), non_blocking=True)
+            self._masked.add(slot)
+        elif slot in self._masked:
+            self.attn[slot].fill_(1)
+            self._masked.discard(slot)
+
+    def run(self, clip, ids=None, attn=None):
+        """clip: one [T,3,H,W] tensor; ids / attn: up to CLIPS [1,L] tensors each (or None: the staged tokens stay)."""
+        self.stage_video(clip)
+        for s in range(0 if ids is None else len(ids)):
+            self.stage_inputs(ids[s], None if attn is None else attn[s], slot=s)
+        return self.replay()
+
+
+def shared_group_pipeline_class(slots: int):
+    """The shared-video pipeline for `slots` expressions of one clip per replay (any count >= 1)."""
+    if int(slots) != slots or slots < 1:
+        raise ValueError("a shared-video pipeline has at least one expression slot")
+    return type(f"SharedVideo{int(slots)}PipelinedClipGraph", (SharedVideoPipelinedClipGraph,), {"CLIPS": int(slots)})
+
+
 def pipeline_class(name: Optional[str] = None):
     """The software pipeline across clips the drivers and bench.py stream through: "one-graph" (default; SOC_PIPELINE
     overrides) or "two-stream".  Same GPU time per clip within the box-to-box spread (tools/experiments/pipeline_ab.py in

@@ -21,7 +21,7 @@ import torch
 
 from . import clip_parallel as CP
 from . import postprocessing as P
-from .graph_runner import ClipGraph, PipelinedClipGraph, group_pipeline_class, pipeline_class
+from .graph_runner import ClipGraph, PipelinedClipGraph, group_pipeline_class, pipeline_class, shared_group_pipeline_class
 from .nested_tensor import NestedTensor
 
 
@@ -63,7 +63,7 @@ class ClipInferencer:
     PAD_ID = 1            # RoBERTa <pad>
 
     def __init__(self, model, device="cuda", use_graphs: bool = True, max_graphs: int = 4,
-                 pad_tokens_to: Optional[int] = None, group: int = 1, packed_masks: bool = False):
+                 pad_tokens_to: Optional[int] = None, group: int = 1, packed_masks: bool = False, share_video: bool = False):
         """packed_masks: results carry 'masks_packed' (uint8 [T,H0,RB], one bit per pixel: packed_masks.py) and 'mask_size'
         (H0, W0) instead of 'masks'; a group whose clips share one original size is up-sampled in ONE launch from the record.
         pad_tokens_to: with graphs, pad every expression to this many tokens (<pad> + attention mask 0), so
@@ -81,13 +81,19 @@ class ClipInferencer:
             raise ValueError("group must be a positive clip count")
         self.group = group
         self.packed_masks = bool(packed_masks)
+        # share_video: submit_expressions / run_expressions take ONE clip and all its expressions and run the video side of the
+        # forward once for them (SOC.forward_expressions, graph_runner.shared_group_pipeline_class: `group` expression slots per
+        # replay).  Off, nothing of it is ever constructed.
+        self.share_video = bool(share_video)
+        self._shared: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}      # shared-video pipelines, in _pipes' budget
+        self._shared_active = None   # (key, pipe, [(tag, original_size)] of the expressions in flight)
         self._filling = []           # (tag, original_size) of the clips staged into the group that has not been replayed yet
         self._graphs: Dict[Tuple[int, int, int, int], ClipGraph] = {}
         self._pipes: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}
         self._singles: Dict[Tuple[int, int, int, int], PipelinedClipGraph] = {}     # one-clip pipelines for the remainders of groups
         self._active = None          # (key, pipe, tag of the clip in flight)
         self.stats = {"group_replays": 0, "part_filled_replays": 0, "stale_slots": 0, "remainder_singles": 0,
-                      "weight_reloads_seen": 0}
+                      "weight_reloads_seen": 0, "shared_video_passes": 0, "shared_expressions": 0}
         watched = use_graphs and isinstance(model, torch.nn.Module)      # (anything else has no load_state_dict to watch)
         self._epoch = weights_epoch(model) if watched else None
         self._probe = next(model.parameters(), None) if watched else None        # re-pointed by model.cpu() / .cuda() / .to()
@@ -102,7 +108,7 @@ class ClipInferencer:
         """Drop every graph that was captured under other weights than the model has now.  Two integers per call; not on the
         replay path of a runner (graph_runner), which callers that own their runner drive directly."""
         if self._epoch is not None and self._weights_state() != self._captured_under:
-            if self._active is not None or self._filling:
+            if self._active is not None or self._filling or self._shared_active is not None:
                 raise RuntimeError("the model's weights changed while clips are staged or in flight: drain() before loading weights")
             self.stats["weight_reloads_seen"] += 1
             self.reset()
@@ -110,13 +116,14 @@ class ClipInferencer:
     def reset(self):
         """Drop every captured graph (and with it the packed weight images and geometry constants it held); the next call of a
         geometry captures again.  Needed by hand after in-place edits of single parameters (`p.copy_`) only."""
-        if self._active is not None or self._filling:
+        if self._active is not None or self._filling or self._shared_active is not None:
             raise RuntimeError("clips are staged or in flight: drain() first")
-        if self._graphs or self._pipes or self._singles:
+        if self._graphs or self._pipes or self._singles or self._shared:
             torch.cuda.synchronize(self.device)              # never drop a graph that may still be replaying
         self._graphs.clear()
         self._pipes.clear()
         self._singles.clear()
+        self._shared.clear()
         self._captured_under = self._weights_state()
 
     def _runner(self, held: Dict, key, runner_class):
@@ -160,6 +167,9 @@ class ClipInferencer:
         return res
 
     def _pipeline(self, key):
+        while self._shared and key not in self._pipes and len(self._shared) + len(self._pipes) >= self.max_graphs:
+            torch.cuda.synchronize(self.device)              # shared-video pipelines (drained by now) sit in the same budget
+            self._shared.pop(next(iter(self._shared)))
         return self._runner(self._pipes, key, lambda: pipeline_class() if self.group == 1 else group_pipeline_class(self.group))
 
     def _single_pipeline(self, key):
@@ -213,6 +223,8 @@ class ClipInferencer:
         ids, attn = self._pad_tokens(token_ids)
         key = (T, H, W, ids.shape[-1])
         out = []
+        if self._shared_active is not None:
+            out += self._drain_shared()                           # expressions of a shared-video call are still in flight
         if self._active is not None and self._active[0] != key:
             out += self.drain()                                   # geometry change: finish what is staged and in flight
         pipe = self._pipeline(key)
@@ -250,6 +262,8 @@ class ClipInferencer:
     def drain(self):
         """Finish what is staged and in flight: list of result dicts.  A part-filled group runs with stale partner slots when it
         is at least half full, through the one-clip pipeline otherwise (_remainder_through_singles)."""
+        if self._shared_active is not None:
+            return self._drain_shared()
         if self._active is None:
             return []
         out = []
@@ -262,6 +276,122 @@ class ClipInferencer:
         for rec in pipe.flush():
             out += self._unpack_rows(rec, key, in_flight)
         return out
+
+    # -- shared-video form: one clip, all its expressions, one pass over the video side per replay ----------------
+    def _shared_pipeline(self, key):
+        """The shared-video pipeline of a geometry; it and the pipelines of _pipes share one budget of max_graphs."""
+        if key not in self._shared:
+            while len(self._shared) + len(self._pipes) >= self.max_graphs:
+                torch.cuda.synchronize(self.device)          # never drop a graph that may still be replaying
+                held = self._pipes if self._pipes else self._shared
+                held.pop(next(iter(held)))
+            self._shared[key] = shared_group_pipeline_class(self.group)(self.model, *key, self.device)
+        return self._shared[key]
+
+    def _pad_expressions(self, token_ids, at_least: Optional[int]):
+        """[ids [1,L_e]] -> ([ids [1,L]], [attn [1,L] or None]) with L = the longest expression (`at_least`, if longer):
+        <pad> + attention mask 0 behind the shorter ones, what tokenizer(..., padding="longest") does."""
+        L = max(int(t.numel()) for t in token_ids)
+        if at_least is not None:
+            L = max(L, at_least)
+        ids, attns = [], []
+        for t in token_ids:
+            t = t.view(1, -1)
+            extra = L - t.shape[-1]
+            if extra:
+                attns.append(torch.cat([torch.ones_like(t), t.new_zeros(1, extra)], 1))
+                t = torch.cat([t, t.new_full((1, extra), self.PAD_ID)], 1)
+            else:
+                attns.append(None)
+            ids.append(t)
+        return ids, attns
+
+    def _unpack_shared(self, rec: torch.Tensor, key, filled):
+        """rec [group, R] of a shared-video replay; filled: (tag, original_size) of its filled slots (one clip: one size).  The
+        rows behind them are stale slots and are never handed out."""
+        packed = None
+        osz = filled[0][1]
+        if self.packed_masks and osz is not None and len(filled) > 1 and rec.stride(1) == 1:
+            from . import packed_masks as PM            # K6b over the filled rows, read where the record holds them
+            T, H, W, _ = key
+            first = rec[0, 1 + T * self.model.num_queries:].view(T, -(-H // 4), -(-W // 4))
+            packed = PM.upsample_threshold_bits(first, (int(osz[0]), int(osz[1])), clip_stride=rec.stride(0), clips=len(filled))
+        return [self._unpack(rec[s], key, tag, size, packed=None if packed is None else packed[s])
+                for s, (tag, size) in enumerate(filled)]
+
+    def _drain_shared(self):
+        key, pipe, in_flight = self._shared_active
+        self._shared_active = None
+        out = []
+        for rec in pipe.flush():
+            out += self._unpack_shared(rec, key, in_flight)
+        return out
+
+    @torch.no_grad()
+    def submit_expressions(self, clip: torch.Tensor, token_ids, tags, original_size=None):
+        """Streaming form for share_video=True: ONE clip [T,3,H,W] and the E expressions of it (token_ids: E tensors [1,L_e],
+        tags: E tags).  The expressions fill the `group` slots of the shared-video pipeline -- E > group: ceil(E / group)
+        replays of the staged clip; a part-filled replay runs with stale slots whose records are dropped -- and every replay
+        runs the video side once.  Returns the list of result dicts that became available (those of the replay before, as
+        submit does; drain() returns the rest), in the order the expressions were given, each what submit yields for
+        (clip, that expression)."""
+        if not (self.use_graphs and self.share_video):
+            raise RuntimeError("submit_expressions() needs use_graphs=True and share_video=True")
+        if len(token_ids) != len(tags) or not len(token_ids):
+            raise ValueError("submit_expressions takes one tag per expression and at least one expression")
+        self._check_weights()
+        T, _, H, W = clip.shape
+        ids, attns = self._pad_expressions(token_ids, self.pad_tokens_to)
+        key = (T, H, W, ids[0].shape[-1])
+        out = []
+        if self._active is not None:
+            out += self.drain()                                   # clips of the unshared stream are staged or in flight
+        if self._shared_active is not None and self._shared_active[0] != key:
+            out += self._drain_shared()                           # geometry change
+        pipe = self._shared_pipeline(key)
+        for at in range(0, len(ids), self.group):
+            if at == 0:
+                pipe.stage_video(clip)                            # the later replays of this call read the same static clip
+            filled = []
+            for s in range(min(self.group, len(ids) - at)):
+                pipe.stage_inputs(ids[at + s], attns[at + s], slot=s)
+                filled.append((tags[at + s], original_size))
+            rec = pipe.replay()
+            self.stats["shared_video_passes"] += 1
+            self.stats["shared_expressions"] += len(filled)
+            self.stats["stale_slots"] += self.group - len(filled)
+            in_flight = self._shared_active[2] if self._shared_active is not None else []
+            self._shared_active = (key, pipe, filled)
+            if rec is not None and in_flight:
+                if at + self.group < len(ids):                    # another replay of this call overwrites the record the results view
+                    rec = rec.clone()
+                out += self._unpack_shared(rec, key, in_flight)
+        return out
+
+    @torch.no_grad()
+    def run_expressions(self, clip: torch.Tensor, token_ids, original_size=None):
+        """Eager form for share_video=True (use_graphs=False): ONE clip and its E expressions through
+        SOC.forward_expressions -> E result dicts, each what __call__ gives for (clip, that expression)."""
+        if not self.share_video or self.use_graphs:
+            raise RuntimeError("run_expressions() is the eager shared-video form: share_video=True, use_graphs=False")
+        T, _, H, W = clip.shape
+        ids, attns = self._pad_expressions(token_ids, None)       # eager: no graph geometry to keep, pad to the longest only
+        ids = torch.cat(ids, 0)
+        attn = torch.cat([torch.ones_like(ids[:1]) if a is None else a for a in attns], 0)
+        samples = NestedTensor(clip[:, None], torch.zeros(T, 1, H, W, dtype=torch.bool, device=clip.device), unpadded=True)
+        out = self.model.forward_expressions(samples, {"input_ids": ids, "attention_mask": attn},
+                                             [[{"size": (H, W)}] for _ in range(T)])
+        self.stats["shared_video_passes"] += 1
+        self.stats["shared_expressions"] += ids.shape[0]
+        results = []
+        for e in range(ids.shape[0]):
+            one = {"pred_cls": out["pred_cls"][:, e:e + 1], "pred_masks": out["pred_masks"][:, e:e + 1]}
+            idx, masks = P.select_trajectory(one)
+            res = {"query": idx, "mask_logits": masks, "pred_cls": one["pred_cls"][:, 0, :, 0], "record": None}
+            if original_size is not None:
+                self._masks_into(res, masks, original_size)
+            results.append(res)
+        return results
 
     @torch.no_grad()
     def forward_clip(self, clip: torch.Tensor, token_ids: torch.Tensor):
@@ -366,8 +496,10 @@ def _run_dataset(a):
     driver = infer_refytb if a.dataset == "refytb" else infer_davis
     model = model.to(dev).eval()
     engine = ClipInferencer(model, dev, use_graphs=a.graphs, pad_tokens_to=32, group=a.group if a.graphs else 1,
-                            packed_masks=a.packed_masks)   # shared across passes
+                            packed_masks=a.packed_masks, share_video=a.share_video)   # shared across passes
     extra = {"packed_masks": True} if a.packed_masks else {}
+    if a.share_video:
+        extra.update(share_video=True)
     if a.eval_davis:
         if a.dataset != "davis":
             raise RuntimeError("--eval-davis scores the output of --dataset davis")
@@ -422,6 +554,10 @@ def parse_args(argv=None):
     ap.add_argument("--packed-masks", action="store_true",
                     help="--dataset refytb: masks leave the GPU bit-packed (one bit per pixel, packed_masks.py) and the PNG files are "
                          "encoded from the bits; same files as without the flag")
+    ap.add_argument("--share-video", action="store_true",
+                    help="--dataset refytb / davis: all expressions of a video (davis: of a 36-frame chunk) go through the model in "
+                         "one call that runs Video-Swin and the rest of the video side once for them; with --graphs they fill the "
+                         "--group slots of the shared-video graph.  Same files as without the flag")
     ap.add_argument("--words", type=int, default=0, help="--make-synthetic: fixed number of words per expression")
     ap.add_argument("--repeat", type=int, default=1, help="run the driver this many times, report the last (warm) pass")
     ap.add_argument("--gpus", "-ng", type=int, default=None,
@@ -432,6 +568,8 @@ def parse_args(argv=None):
         ap.error("--packed-masks applies to --dataset refytb (the DAVIS driver writes label maps, which are not one-bit data)")
     if a.eval_refytb and a.dataset != "refytb":
         ap.error("--eval-refytb scores the output of --dataset refytb (--eval-davis is the flag of --dataset davis)")
+    if a.share_video and not a.dataset:
+        ap.error("--share-video applies to the dataset drivers (--dataset refytb | davis)")
     if a.group is None:
         a.group = 8 if a.graphs else 1
     a.gpus_given = a.gpus is not None

@@ -106,8 +106,10 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         decode_workers: int = 8, writer_workers: int = 16, palette: Optional[Sequence[int]] = None,
         videos: Optional[Sequence[str]] = None, annotators: int = 4,
         engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1,
-        eval_root: Optional[str] = None, eval_task: str = "unsupervised") -> Dict:
-    """eval_root: a DAVIS tree (ImageSets/2017/val.txt, Annotations[_unsupervised]/480p).  When given, every annotator's label
+        eval_root: Optional[str] = None, eval_task: str = "unsupervised", share_video: bool = False) -> Dict:
+    """share_video: all (object, annotator) expressions of a chunk go to the engine in ONE call (ClipInferencer(share_video=True)),
+    which runs the video side of the forward once for them; the files and the scoring are as without it.
+    eval_root: a DAVIS tree (ImageSets/2017/val.txt, Annotations[_unsupervised]/480p).  When given, every annotator's label
     maps are scored against it on the device, as the reference's eval_davis.py scores the PNGs afterwards (davis_eval, K27):
     stats["jf"] holds the global row per annotator and their mean, and the two CSVs are written into each anno_<a> directory.
     The PNGs and everything else the driver does are the same with and without it."""
@@ -125,7 +127,10 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         if world != 1:
             raise ValueError("eval_root: the tables cover every video of the set, so scoring runs in one process (world = 1)")
         scorer = _Scorer(eval_root, eval_task, todo, annotators, device)
-    engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group)
+    engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group,
+                                      share_video=share_video)
+    if share_video and not getattr(engine, "share_video", False):
+        raise ValueError("share_video of run() needs an engine built with share_video=True")
     cache = clip_io.VideoClipCache(clip_io.FramePreprocessor(device, size, max_size), workers=decode_workers)
     stats = {"videos": 0, "expressions": 0, "frames": 0, "seconds_input": 0.0, "seconds_model": 0.0}
     pending = []
@@ -174,6 +179,37 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
             exp_ids = list(exps.keys())
             num_obj = len(exp_ids) // annotators
             starts = list(range(0, len(frames), CLIP_LEN))
+            if share_video:
+                # chunks outermost, and per chunk every (annotator, object) expression in one engine call
+                ids = [[tokenize(exps[exp_ids[obj * annotators + anno]]["exp"]).to(device) for obj in range(num_obj)]
+                       for anno in range(annotators)]
+                vjobs = [{"got": [[None] * len(starts) for _ in range(num_obj)], "left": num_obj * len(starts), "orig": None,
+                          "save_dir": os.path.join(out_dir, f"anno_{anno}", video), "video": video, "anno": anno}
+                         for anno in range(annotators)]
+                waiting.extend(vjobs)
+                pairs = [(anno, obj) for anno in range(annotators) for obj in range(num_obj)]
+                for ci, c0 in enumerate(starts):
+                    t1 = time.perf_counter()
+                    clip, orig = cache.get(clip_io.frame_paths(img_folder, video, frames[c0:c0 + CLIP_LEN]))
+                    stats["seconds_input"] += time.perf_counter() - t1
+                    for job in vjobs:
+                        job["orig"] = orig
+                    tokens = [ids[anno][obj] for anno, obj in pairs]
+                    tags = [(vjobs[anno], obj, ci) for anno, obj in pairs]
+                    if not pairs:
+                        continue
+                    if streaming:
+                        for res in engine.submit_expressions(clip, tokens, tags):       # results of the PREVIOUS replay, if any
+                            place(res)
+                    else:
+                        for res, tag in zip(engine.run_expressions(clip, tokens), tags):
+                            res["tag"] = tag
+                            place(res)
+                    merge_ready(writers)
+                stats["expressions"] += num_obj * annotators
+                stats["frames"] += num_obj * annotators * len(frames)
+                stats["videos"] += 1
+                continue
             for anno in range(annotators):
                 ids = [tokenize(exps[exp_ids[obj * annotators + anno]]["exp"]).to(device) for obj in range(num_obj)]
                 job = {"got": [[None] * len(starts) for _ in range(num_obj)], "left": num_obj * len(starts), "orig": None,

@@ -142,8 +142,10 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
         split: str = "valid", size: int = 360, max_size: Optional[int] = 640, use_graphs: bool = False,
         decode_workers: int = 8, writer_workers: int = 16, videos: Optional[Sequence[str]] = None,
         engine: Optional[ClipInferencer] = None, pad_tokens_to: Optional[int] = 32, group: int = 1,
-        packed_masks: bool = False, eval_root: Optional[str] = None) -> Dict:
-    """Process this rank's videos; returns counters + timings.  eval_root: a tree with <split>/Annotations and a
+        packed_masks: bool = False, eval_root: Optional[str] = None, share_video: bool = False) -> Dict:
+    """Process this rank's videos; returns counters + timings.  share_video: all expressions of a video go to the engine in ONE
+    call (ClipInferencer(share_video=True): submit_expressions with graphs, run_expressions without), which runs the video side
+    of the forward once for them; files, tags, scoring and packed masks are as without it.  eval_root: a tree with <split>/Annotations and a
     meta_expressions.json whose expressions carry obj_id.  When given, every expression's masks are scored against the object it
     names while they are on the device (refytb_eval, K27b: the bits K6b wrote are read in place, the expressions of one video
     that arrive in one group in one call; byte masks are packed on the device first): stats["jf"] holds the global row and the
@@ -161,7 +163,9 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
             raise ValueError("eval_root: the tables cover every video of the set, so scoring runs in one process (world = 1)")
         scorer = _Scorer(eval_root, split, todo, device)
     engine = engine or ClipInferencer(model, device, use_graphs=use_graphs, pad_tokens_to=pad_tokens_to, group=group,
-                                      packed_masks=packed_masks)
+                                      packed_masks=packed_masks, share_video=share_video)
+    if share_video and not getattr(engine, "share_video", False):
+        raise ValueError("share_video of run() needs an engine built with share_video=True")
     if bool(getattr(engine, "packed_masks", False)) != bool(packed_masks):
         raise ValueError("packed_masks of run() and of the engine it was given disagree")
     cache = clip_io.VideoClipCache(clip_io.FramePreprocessor(device, size, max_size), workers=decode_workers)
@@ -256,7 +260,28 @@ def run(model, tokenize: Tokenize, root: str, out_dir: str, rank: int = 0, world
                     cache.prefetch(clip_io.frame_paths(img_folder, nxt, data[nxt]["frames"]))
             if scorer is not None:
                 scorer.begin(video, len(data[video]["expressions"]))
-            for exp_id, item in data[video]["expressions"].items():
+            expressions = data[video]["expressions"]
+            if share_video and expressions:
+                t1 = time.perf_counter()
+                clip, orig = cache.get(paths)
+                ids = [tokenize(item["exp"]).pin_memory().to(device, non_blocking=True) for item in expressions.values()]
+                t2 = time.perf_counter()
+                tags = [(os.path.join(out_dir, video, exp_id), frames, video, exp_id) for exp_id in expressions]
+                for tag in tags:
+                    os.makedirs(tag[0], exist_ok=True)
+                if streaming:
+                    handle(engine.submit_expressions(clip, ids, tags, orig))   # results of the PREVIOUS replay, if any
+                else:
+                    results = engine.run_expressions(clip, ids, orig)
+                    for res, tag in zip(results, tags):
+                        res["tag"] = tag
+                    handle(results)
+                stats["seconds_input"] += t2 - t1
+                stats["seconds_model"] += time.perf_counter() - t2
+                stats["expressions"] += len(ids)
+                stats["frames"] += len(frames) * len(ids)
+                expressions = {}
+            for exp_id, item in expressions.items():
                 t1 = time.perf_counter()
                 clip, orig = cache.get(paths)                                  # decoded / resized once per video
                 ids = tokenize(item["exp"]).pin_memory().to(device, non_blocking=True)

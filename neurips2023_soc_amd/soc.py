@@ -20,7 +20,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import fused, hot_ops
+from . import fused, hot_ops, xattn_shared
 from .deformable_transformer import build_deforamble_transformer
 from .nested_tensor import NestedTensor
 from .position_encoding import PositionEmbeddingSine1D
@@ -389,6 +389,169 @@ class SOC(nn.Module):
         _, ctx = self.transformer.encode(srcs, masks, poses, token_major=True, unpadded=unpadded, maps=False)
         return {"ctx": ctx, "feats0": feats[0], "lang_last": lang_last, "word_pad": word_pad,
                 "sentence": sentence, "B": B, "T": T}
+
+    # ------------------------------------------------------------------ one clip, E expressions (shared video side)
+    def _levels_forked(self, device, fork: bool, run_level):
+        """[run_level(l) for every feature level], the two finest levels on the calling stream and the coarse ones beside them
+        on the side stream -- the split forward_fuse_encode uses."""
+        n_levels = self.num_feature_levels
+        side = self._side_stream(device) if (device.type == "cuda" and fork) else None
+        if side is None or n_levels <= 2:
+            return [run_level(l) for l in range(n_levels)]
+        main = torch.cuda.current_stream(device)
+        out = [None] * n_levels
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            for l in range(n_levels - 1, 1, -1):
+                out[l] = run_level(l)
+        for l in (0, 1):
+            out[l] = run_level(l)
+        main.wait_stream(side)
+        return out
+
+    @staticmethod
+    def _repeat_frames(x, E: int):
+        """[n, c, h, w] -> [E * n, c, h, w], the n frames E times over (one copy); a channels-last map stays channels-last."""
+        if E == 1:
+            return x
+        tok = x.permute(0, 2, 3, 1)
+        if tok.is_contiguous():
+            return tok.repeat(E, 1, 1, 1).permute(0, 3, 1, 2)
+        return x.repeat(E, 1, 1, 1)
+
+    @torch.no_grad()
+    @_in_model_mode
+    def forward_video_shared(self, samples: NestedTensor, fork: bool = True):
+        """Everything of the forward that is a function of the frames alone, for ONE clip (B = 1): what forward_video returns,
+        plus per feature level the projected token rows '(t h w) c' (input_proj + GroupNorm; the stride-2 extra level), their
+        mask and position encoding and `vlf`'s query projection of the rows, plus `lvf`'s key / value projections of the last
+        backbone level.  forward_fuse_encode_shared joins it with the text state of any number of expressions."""
+        if samples.tensors.shape[1] != 1:
+            raise ValueError(f"forward_video_shared takes one clip, got a batch of {samples.tensors.shape[1]}")
+        vs = self.forward_video(samples)
+        feats, fmasks, pos, unpadded = vs["feats"], vs["masks"], vs["pos"], vs["unpadded"]
+        device = feats[0].device
+        T = pos[-1].shape[0]
+        backbone_levels = list(zip(feats[-3:], fmasks[-3:], pos[-3:]))
+        if self.num_feature_levels > len(backbone_levels) + 1:
+            raise NotImplementedError("more than one extra feature level is not used by any shipped config")
+        C = self.vlf.multihead_attn.embed_dim
+        wv, bv = self.vlf.multihead_attn.in_proj_weight, self.vlf.multihead_attn.in_proj_bias
+        wl, bl = self.lvf.multihead_attn.in_proj_weight, self.lvf.multihead_attn.in_proj_bias
+
+        def video_level(l):
+            lv = {}
+            if l < len(backbone_levels):
+                src, mask, pos_l = backbone_levels[l]
+                h, w = src.shape[-2:]
+                seq = self._project_level(l, src, 1, T, clip_major=True)[0]
+                if l == len(backbone_levels) - 1:         # lvf reads this level alone: its keys (rows + pos) and values
+                    pos_seq = self._seq_clip_major(pos_l, 1, T)[0]
+                    if fused.is_small(seq):
+                        k, v = fused.linear_multi(seq, [(wl[C:2 * C], bl[C:2 * C], True), (wl[2 * C:], bl[2 * C:], False)], pos_seq)
+                    else:
+                        k = fused.linear(seq, wl[C:2 * C], bl[C:2 * C], add=pos_seq)
+                        v = fused.linear(seq, wl[2 * C:], bl[2 * C:])
+                    lv.update(lvf_k=k, lvf_v=v, lvf_mask=mask.view(1, T, h, w).reshape(1, -1))
+            else:                          # the extra level: 3x3 / stride-2 conv of the coarsest backbone map
+                src = self.input_proj[l](feats[-1])
+                mask = resize_pad_mask(vs["sample_mask"], src.shape[-2:], unpadded)
+                pos_l = self.backbone.position_encoding(NestedTensor(src, mask), unpadded)
+                h, w = src.shape[-2:]
+                seq = self._seq_clip_major(src, 1, T)[0]
+            lv.update(seq=seq, mask=mask, pos=pos_l, hw=(h, w), vlf_q=fused.linear(seq, wv[:C], bv[:C]))
+            return lv
+
+        return {**vs, "T": T, "levels": self._levels_forked(device, fork, video_level)}
+
+    @torch.no_grad()
+    @_in_model_mode
+    def forward_fuse_encode_shared(self, video_state, text_state, fork: bool = True, feats0_out=None):
+        """Stage B for one clip and the E expressions of `text_state` (forward_text_state of E token rows): the hand-over state
+        forward_fuse_encode returns for B = E -- forward_tail, group_tail, slice_state and split_state take it as it is.
+        `vlf`'s core is K3s (xattn_shared.py): the level's projected query rows are read once for all expressions.  What is
+        still made E times over from the shared tensors: the level rows as the `mul=` operand of vlf's output projection, the
+        levels' masks and position encodings, and the stride-4 backbone map (the FPN's stage-0 lateral)."""
+        words, word_pad, text_pos, sentence = (text_state[k] for k in ("words", "word_pad", "text_pos", "sentence"))
+        levels, T, unpadded = video_state["levels"], video_state["T"], video_state["unpadded"]
+        device = words.device
+        E = words.shape[1]
+        words = words.transpose(0, 1).contiguous()                   # [E,L,C]: batch-first, like a launch group
+        text_pos = text_pos.transpose(0, 1).contiguous()
+        vlf, lvf = self.vlf.multihead_attn, self.lvf.multihead_attn
+        C = vlf.embed_dim
+        wv, bv = vlf.in_proj_weight, vlf.in_proj_bias
+        # vlf's keys / values are the words: the same for every level
+        if fused.is_small(words):
+            wk, wvv = fused.linear_multi(words, [(wv[C:2 * C], bv[C:2 * C], True), (wv[2 * C:], bv[2 * C:], False)], text_pos)
+        else:
+            wk = fused.linear(words, wv[C:2 * C], bv[C:2 * C], add=text_pos)
+            wvv = fused.linear(words, wv[2 * C:], bv[2 * C:])
+
+        def fuse_level(l):
+            lv = levels[l]
+            h, w = lv["hw"]
+            o = xattn_shared.mha_core_shared_q(lv["vlf_q"], wk, wvv, vlf.num_heads, word_pad)          # [E,Lq,C]
+            fused_l = fused.linear(o, vlf.out_proj.weight, vlf.out_proj.bias, mul=lv["seq"][None].expand(E, -1, -1))
+            mask = lv["mask"].repeat(E, 1, 1) if E > 1 else lv["mask"]
+            if unpadded:                                             # cached per geometry, as for a group of E clips
+                pos_l = self.backbone.position_encoding(NestedTensor(lv["pos"], mask), True)
+            else:
+                pos_l = self._repeat_frames(lv["pos"], E)
+            lang = None
+            if "lvf_k" in lv:
+                # lvf: every expression's word rows against the ONE set of pixel keys -- K3 with the E * L rows as its queries
+                q = fused.linear(words, lvf.in_proj_weight[:C], lvf.in_proj_bias[:C])
+                lo = hot_ops.mha_core(q.reshape(1, -1, C), lv["lvf_k"][None], lv["lvf_v"][None], lvf.num_heads,
+                                      lv["lvf_mask"], batch_first=True)
+                lang = fused.linear(lo.view(E, -1, C), lvf.out_proj.weight, lvf.out_proj.bias, mul=words)
+                lang = lang.transpose(0, 1).contiguous()             # [L,E,C] like the sequence-first path
+            return fused_l.reshape(E * T, h * w, C), mask, pos_l, lang
+
+        per_level = self._levels_forked(device, fork, fuse_level)
+        lang_last = next(p[3] for p in per_level if p[3] is not None)
+        _, ctx = self.transformer.encode([p[0] for p in per_level], [p[1] for p in per_level], [p[2] for p in per_level],
+                                         token_major=True, unpadded=unpadded, maps=False)
+        feats0 = video_state["feats"][0]
+        if feats0_out is None:
+            feats0 = self._repeat_frames(feats0, E)
+        else:
+            # a graph runner's static hand-over buffer [E * T, c, h, w]: the copies are written there, as contiguous token-major
+            # rows where the maps are channels-last; a map that was produced IN its first slot is not copied onto itself
+            src, dst = feats0.permute(0, 2, 3, 1), feats0_out.permute(0, 2, 3, 1)
+            if not (src.is_contiguous() and dst.is_contiguous()):
+                src, dst = feats0, feats0_out
+            first = 1 if feats0.data_ptr() == feats0_out.data_ptr() else 0
+            if first < E:
+                dst.view(E, *src.shape)[first:].copy_(src[None])
+            feats0 = feats0_out
+        return {"ctx": ctx, "feats0": feats0, "lang_last": lang_last, "word_pad": word_pad, "sentence": sentence, "B": E, "T": T}
+
+    @torch.no_grad()
+    def forward_expressions(self, samples: NestedTensor, text_queries, targets, fork: bool = True):
+        """One clip (samples.tensors [T,1,3,H,W]) and E expressions of it (strings, or pre-tokenised [E,L]) -> forward's output
+        dict with B = E: every expression gets what `model(samples, None, [that expression], targets)` gives (to f32
+        rounding), from ONE pass over the video side.  targets[t][0]['size'] is the clip's; targets with E entries per frame are
+        taken as they are."""
+        if self.training:
+            raise RuntimeError("this build of SOC is inference-only: call model.eval()")
+        device = samples.tensors.device
+        side = self._side_stream(device) if (device.type == "cuda" and fork) else None
+        if side is not None:                     # RoBERTa beside Video-Swin, as in forward_backbone
+            main = torch.cuda.current_stream(device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                tx = self.forward_text_state(text_queries, device)
+            vs = self.forward_video_shared(samples)
+            main.wait_stream(side)
+        else:
+            tx = self.forward_text_state(text_queries, device)
+            vs = self.forward_video_shared(samples, fork=False)
+        state = self.forward_fuse_encode_shared(vs, tx, fork=fork)
+        E = state["B"]
+        if len(targets[0]) != E:
+            targets = [[frame[0]] * E for frame in targets]
+        return self.forward_tail(state, targets, fork=fork, voc_per_clip=True)
 
     @torch.no_grad()
     @_in_model_mode
