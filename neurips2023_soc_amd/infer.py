@@ -8,6 +8,7 @@ multi-GPU form of its `sub_processor` fan-out (infer_refytb.py:84-109, SURVEY.md
     python -m neurips2023_soc_amd.infer --dataset refytb --root DATA --out RUNS [--tokenizer DIR] [--checkpoint CKPT]
     python -m neurips2023_soc_amd.infer --dataset davis --root DATA --out RUNS --make-synthetic 4   # writes DATA first
     python -m neurips2023_soc_amd.infer --dataset refytb --root DATA --out RUNS --packed-masks --eval-refytb GT   # scores RUNS
+    python -m neurips2023_soc_amd.infer --dataset jhmdb --root DATA --out RUNS [--samples FILE] [--save-predictions]   # P@K, IoU
 """
 from __future__ import annotations
 
@@ -457,6 +458,28 @@ def load_tokenizer(path: str):
     return tokenize
 
 
+def _run_jhmdb(a, dev, rank: int, world: int):
+    """The JHMDB-Sentences evaluation (infer_jhmdb.py): eager forwards with valid_indices, K6c, the metrics dict."""
+    from . import build_model, default_args, infer_jhmdb, synthetic_dataset
+    from . import weights as W
+    if a.make_synthetic and rank == 0:
+        infer_jhmdb.make_synthetic(a.root, videos=a.make_synthetic, frames=max(a.frames, 4) + 4)
+    args = default_args(a.backbone, text_encoder_random_init=True)
+    args.dataset_name = "jhmdb_sentences"
+    model, _, _ = build_model(args)
+    if a.checkpoint:
+        load_checkpoint(model, a.checkpoint)
+    else:
+        W.load_synthetic(model, 2023)
+    tokenize = load_tokenizer(a.tokenizer) if a.tokenizer else synthetic_dataset.HashTokenizer()
+    model = model.to(dev).eval()
+    for _ in range(max(a.repeat, 1)):
+        stats = infer_jhmdb.run(model, tokenize, a.root, a.out, rank, world, dev, samples_file=a.samples, seed=a.seed,
+                                group=a.group, save_predictions=a.save_predictions)
+    stats["samples_per_s"] = stats["samples"] / stats["seconds"]
+    print(json.dumps({"rank": rank, "world": world, **stats}))
+
+
 def _run_dataset(a):
     """infer_refytb.py / infer_davis.py `main`: one process per GPU over a static split of the videos
     (reference infer_refytb.py:84-109), no collective -- every rank writes its own PNGs."""
@@ -468,6 +491,8 @@ def _run_dataset(a):
         raise RuntimeError(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    if a.dataset == "jhmdb":
+        return _run_jhmdb(a, dev, rank, world)
     if a.make_synthetic and rank == 0:
         expressions = 8 if a.dataset == "davis" else 3
         synthetic_dataset.make_dataset(a.root, videos=a.make_synthetic, frames=a.frames, expressions=expressions,
@@ -529,7 +554,7 @@ def parse_args(argv=None):
     ap.add_argument("--height", type=int, default=360)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--orig", type=int, nargs=2, default=[720, 1280], help="original frame size for the output masks")
-    ap.add_argument("--dataset", choices=["refytb", "davis"], help="run a dataset driver instead of the clip stream")
+    ap.add_argument("--dataset", choices=["refytb", "davis", "jhmdb"], help="run a dataset driver instead of the clip stream")
     ap.add_argument("--root", help="dataset root (JPEGImages + meta_expressions, reference layout)")
     ap.add_argument("--out", help="output directory for the mask PNGs")
     ap.add_argument("--tokenizer", help="directory with RobertaTokenizerFast files (default: synthetic hash tokenizer)")
@@ -558,18 +583,39 @@ def parse_args(argv=None):
                     help="--dataset refytb / davis: all expressions of a video (davis: of a 36-frame chunk) go through the model in "
                          "one call that runs Video-Swin and the rest of the video side once for them; with --graphs they fill the "
                          "--group slots of the shared-video graph.  Same files as without the flag")
+    ap.add_argument("--samples", metavar="FILE",
+                    help="--dataset jhmdb: the samples to score, in the reference's metadata format (JSON rows of [video_id, "
+                         "frame_path, masks_path, total_frames, query]; only the frame number of frame_path is used).  Without "
+                         "it three frames per (video, query) are drawn from --seed and written to --out/samples.json; the "
+                         "paper's numbers need the reference's own samples file")
+    ap.add_argument("--seed", type=int, default=0, help="--dataset jhmdb: seed of the drawn samples")
+    ap.add_argument("--save-predictions", action="store_true",
+                    help="--dataset jhmdb: also write --out/predictions.json, COCO results of all queries of every sample with "
+                         "uncompressed run-length counts")
     ap.add_argument("--words", type=int, default=0, help="--make-synthetic: fixed number of words per expression")
     ap.add_argument("--repeat", type=int, default=1, help="run the driver this many times, report the last (warm) pass")
     ap.add_argument("--gpus", "-ng", type=int, default=None,
                     help="GPUs of this node; >1 without an outer launcher starts one rank per GPU (reference -ng).  "
                          "Default: WORLD_SIZE under an outer launcher, 1 otherwise; an explicit value must equal WORLD_SIZE")
     a = ap.parse_args(argv)
+    if a.packed_masks and a.dataset == "jhmdb":
+        ap.error("--packed-masks applies to --dataset refytb (--dataset jhmdb writes no mask files, and its masks leave the "
+                 "kernel bit-packed whatever the flag says)")
     if a.packed_masks and a.dataset != "refytb":
         ap.error("--packed-masks applies to --dataset refytb (the DAVIS driver writes label maps, which are not one-bit data)")
     if a.eval_refytb and a.dataset != "refytb":
         ap.error("--eval-refytb scores the output of --dataset refytb (--eval-davis is the flag of --dataset davis)")
     if a.share_video and not a.dataset:
         ap.error("--share-video applies to the dataset drivers (--dataset refytb | davis)")
+    if a.share_video and a.dataset == "jhmdb":
+        ap.error("--share-video applies to --dataset refytb | davis (a JHMDB-Sentences video has one expression: there is "
+                 "nothing to share)")
+    if a.eval_davis and a.dataset == "jhmdb":
+        ap.error("--eval-davis scores the output of --dataset davis (--dataset jhmdb prints its own metrics)")
+    if a.graphs and a.dataset == "jhmdb":
+        ap.error("--graphs applies to --dataset refytb | davis (the centre-frame forward of --dataset jhmdb runs eagerly)")
+    if (a.samples or a.save_predictions) and a.dataset != "jhmdb":
+        ap.error("--samples and --save-predictions apply to --dataset jhmdb")
     if a.group is None:
         a.group = 8 if a.graphs else 1
     a.gpus_given = a.gpus is not None

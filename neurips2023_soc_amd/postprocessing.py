@@ -2,7 +2,8 @@
 
 select_trajectory + upsample_and_threshold restate infer_refytb.py:216-231;
 ReferYoutubeVOSPostProcess mirrors models/postprocessing.py:193-234; merge_davis_objects the
-multi-object argmax of infer_davis.py:264-272.
+multi-object argmax of infer_davis.py:264-272; A2DSentencesPostProcess models/postprocessing.py:10-55
+(the centre-frame protocol of A2D-Sentences / JHMDB-Sentences, on K6c).
 """
 from __future__ import annotations
 
@@ -67,11 +68,56 @@ class ReferYoutubeVOSPostProcess(nn.Module):
         return preds
 
 
+class A2DSentencesPostProcess(nn.Module):
+    """The centre-frame post-processor of A2D-Sentences / JHMDB-Sentences (reference models/postprocessing.py:10-55): per
+    annotated frame the scores of all queries and their masks at the frame's original size.
+
+    outputs: 'pred_cls' [t,b,Q,1] and 'pred_masks' [t*b,Q,h,w] (the reference's caller flattens it; [t,b,Q,h,w] is flattened
+    here).  -> per frame {'scores': [Q] = pred_cls[..., 0].sigmoid(), 'masks': float32 [Q,1,oh,ow] of zeros and ones,
+    'rle_masks': per query {'size': [oh, ow], 'counts': [...]}}.  On CUDA tensors the masks are K6c's (center_frame.py: one
+    launch for all frames and queries); CPU tensors take the reference's torch ops.
+
+    'counts' are UNCOMPRESSED COCO run lengths -- column-major runs, the first one of zeros -- built on the host from the
+    packed bits.  The compressed string form the reference stores is pycocotools' encoding, which is not available here and
+    is not produced; pycocotools' frPyObjects turns the uncompressed form into it."""
+
+    @torch.inference_mode()
+    def forward(self, outputs, resized_padded_sample_size, resized_sample_sizes, orig_sample_sizes):
+        from . import center_frame as CF
+        from . import packed_masks
+        scores = outputs["pred_cls"].flatten(0, 1)[..., 0].sigmoid()
+        pred_masks = outputs["pred_masks"]
+        if pred_masks.dim() == 5:
+            pred_masks = pred_masks.flatten(0, 1)
+        padded = tuple(int(v) for v in resized_padded_sample_size)
+        resized = [tuple(int(v) for v in s) for s in resized_sample_sizes]
+        original = [tuple(int(v) for v in s) for s in orig_sample_sizes]
+        Q = pred_masks.shape[1]
+        masks, packed = [], []
+        if pred_masks.is_cuda:
+            bits, _ = CF.center_frame_bits(pred_masks.float(), padded, resized, original, masks=True)
+            host = bits.cpu()
+            for n, (oh, ow) in enumerate(original):
+                packed.append(CF.sample_masks(host, original, Q, n).numpy())
+                masks.append(packed_masks.unpack(CF.sample_masks(bits, original, Q, n), ow).unsqueeze(1).float())
+        else:
+            up = F.interpolate(pred_masks, size=padded, mode="bilinear", align_corners=False).sigmoid() > 0.5
+            for f_masks, (rh, rw), (oh, ow) in zip(up, resized, original):
+                m = F.interpolate(f_masks[:, :rh, :rw].unsqueeze(1).float(), size=(oh, ow), mode="nearest")
+                masks.append(m)
+                packed.append(packed_masks.pack(m[:, 0].numpy()))
+        rles = [[{"size": [oh, ow], "counts": CF.rle_counts(plane, (oh, ow))} for plane in planes]
+                for planes, (oh, ow) in zip(packed, original)]
+        return [{"scores": s, "masks": m, "rle_masks": r} for s, m, r in zip(scores, masks, rles)]
+
+
 def build_postprocessors(dataset_name: str):
-    """reference models/soc.py:648-660; only the Ref-YouTube-VOS / DAVIS inference paths are built."""
+    """reference models/soc.py:648-660; the COCO pre-training post-processors are not built."""
+    if dataset_name in ("a2d_sentences", "jhmdb_sentences"):
+        return A2DSentencesPostProcess()
     if dataset_name in ("ref_youtube_vos", "joint"):
         return ReferYoutubeVOSPostProcess()
     if dataset_name == "davis":
         return None
     raise NotImplementedError(f"post-processor for {dataset_name!r} is outside the inference hot path "
-                              "(A2D/JHMDB/COCO evaluation: SURVEY.md section 2, out of scope)")
+                              "(COCO pre-training evaluation: SURVEY.md section 2, out of scope)")

@@ -265,7 +265,9 @@ class SOC(nn.Module):
         """samples.tensors [T,B,3,H,W] + mask [T,B,H,W]; text_queries: B strings (or pre-tokenised);
         targets[0][b]['size'] = (H,W) of the model input.  Returns the reference's output dict:
         pred_masks [T,B,Q,H/4,W/4], pred_cls [T,B,Q,K], pred_boxes [T,B,Q,4], pred_logit [B,Q,C],
-        text_sentence_feature [B,C], aux_outputs []."""
+        text_sentence_feature [B,C], aux_outputs [].
+        valid_indices (None, or one '(b t)' index per clip: the annotated centre frame of A2D / JHMDB-Sentences): Video-Swin
+        sees the whole window, everything behind it the selected frames alone -- the outputs then have T = 1."""
         return self.forward_tail(self.forward_head(samples, valid_indices, text_queries), targets)
 
     @torch.no_grad()
@@ -280,10 +282,9 @@ class SOC(nn.Module):
         """Stage A: RoBERTa ‖ Video-Swin.  -> state for forward_fuse_encode."""
         if self.training:
             raise RuntimeError("this build of SOC is inference-only: call model.eval()")
-        if valid_indices is not None:
-            raise NotImplementedError("valid_indices is only used by the A2D/JHMDB loaders "
-                                      "(reference soc.py:208-215), outside the inference hot path")
         device = samples.tensors.device
+        if valid_indices is not None:
+            valid_indices = self._check_valid_indices(valid_indices, *samples.tensors.shape[:2]).to(device)
         # The text branch (RoBERTa: ~150 latency-bound launches on 10 tokens) and the video backbone
         # are independent until the first vision-language fusion: run them on two HIP streams so the
         # small text kernels hide under the Swin kernels (also captured as a fork/join in ClipGraph).
@@ -298,7 +299,42 @@ class SOC(nn.Module):
         else:
             tx = self.forward_text_state(text_queries, device)
             vs = self.forward_video(samples)
+        if valid_indices is not None:
+            vs = self.select_valid_frames(vs, valid_indices)
         return {**vs, **tx}
+
+    @staticmethod
+    def _check_valid_indices(valid_indices, T: int, B: int) -> torch.Tensor:
+        """valid_indices of a [T,B,...] batch as an int64 tensor: one '(b t)' index per clip, in clip order (the reference sets
+        T = 1 after its selection, models/soc.py:215, so anything else would silently mix the clips' frames)."""
+        idx = torch.as_tensor(valid_indices)
+        if idx.dim() != 1 or idx.is_floating_point() or idx.dtype == torch.bool:
+            raise ValueError(f"valid_indices must be a 1-D integer tensor of '(b t)' frame indices, got {idx.dtype} "
+                             f"{tuple(idx.shape)}")
+        got = [int(v) for v in idx.tolist()]
+        if len(got) != B or any(v < b * T or v >= (b + 1) * T for b, v in enumerate(got)):
+            raise ValueError(f"valid_indices must name exactly one frame of each of the {B} clips of {T} frames, in clip order "
+                             f"(index b * {T} + t for clip b); got {got}")
+        return idx.to(torch.int64)
+
+    @staticmethod
+    def select_valid_frames(video_state, valid_indices: torch.Tensor):
+        """The annotated frames of forward_video's state (reference models/soc.py:208-215, the centre-frame protocol of
+        A2D-Sentences / JHMDB-Sentences): index_select(0, valid_indices) of every backbone level -- level 0 included, it is the
+        FPN's finest lateral --, its mask, every position encoding and the samples' mask.  With one index per clip the state
+        is that of B clips of ONE frame; forward_fuse_encode reads T from it."""
+        def rows(x):
+            if x is None:                       # the stride-4 level has no position encoding (nothing reads it)
+                return None
+            if x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous():           # a channels-last map stays channels-last
+                return x.permute(0, 2, 3, 1).index_select(0, valid_indices).permute(0, 3, 1, 2)
+            return x.index_select(0, valid_indices)
+        out = dict(video_state)
+        out["feats"] = [rows(f) for f in video_state["feats"]]
+        out["masks"] = [rows(m) for m in video_state["masks"]]
+        out["pos"] = [rows(p) for p in video_state["pos"]]
+        out["sample_mask"] = rows(video_state["sample_mask"])
+        return out
 
     @torch.no_grad()
     @_in_model_mode
